@@ -7,8 +7,12 @@ per-env returns are all-gathered over RCCL, one collective per replay on the col
 stream, overlapped with the next replay's kernels.  Actions are synthetic (uniform in the
 action Box, 20 % exact zeros), pre-generated on the device outside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--chargers C] [--no-cpu-baseline]
-        # N > 1: this process measures cpu_baseline, then starts N rank processes itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--chargers C] [--dump-outputs DIR]
+        # the plain run: set up, warm up, time the K days, print the line (`roofline` and `cpu_baseline` null)
+    python bench.py --full [...] [--no-cpu-baseline]
+        # also everything below that takes runs of its own: the CPU baseline, the per-kernel HIP-event
+        # timing of eager days, the copy-probe ceilings and the committed rocprofv3 figures (`roofline`)
+        # N > 1: this process measures cpu_baseline (--full), then starts N rank processes itself
         # (torch.distributed.run as a child process) and exits with their status
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
         [--dist-backend gloo]   # several ranks on one GPU: day returns gathered through host memory
@@ -16,7 +20,12 @@ action Box, 20 % exact zeros), pre-generated on the device outside the timed reg
     and fewer than N visible GPUs.  The line's `dist` object reports the process group's backend and the
     world size it initialised.
 
-Rank 0 prints one JSON line.  `roofline` describes the dominant kernel (the fused step):
+--dump-outputs DIR writes what the last timed day left in the buffers a caller of the day graphs reads, as
+DIR/<name>.npy: the last step's observations (float32), rewards and dones, and every env's return of that day
+(float64); at most 64 MB in all (beyond that the same seeded sample of env rows of every array).  The seed fixes the
+days and the actions, so two builds run with the same arguments can be compared array for array.
+
+Rank 0 prints one JSON line.  With --full, `roofline` describes the dominant kernel (the fused step):
 achieved = SURVEY.md 8(d)'s algorithmic bytes per env-step, B(N) = 40 N + 65 (465 B at N = 10),
 x the envs of one launch / the step kernel's mean duration inside the day graphs: the HIP-event device
 time of a timed day (on the graphs' stream) less the reset kernel, over the T step dispatches -- the
@@ -207,6 +216,30 @@ def copy_ceiling(device, read_bytes, write_bytes, reps=50):
             "gbs_back_to_back": round(tot / (b_us.value * 1e-6) / 1e9, 1)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, venv, seed):
+    """--dump-outputs: what the last timed day left in the buffers the day graphs write, the arrays a caller
+    of EpisodeGraph.launch() reads afterwards: the last step's observations [E, obs_dim] (float32), rewards
+    [E] and dones [E], and every env's return of that day [E] (float64).  Past DUMP_LIMIT_BYTES in all, every
+    array keeps the same seeded sample of env rows (sorted; `env_ids.npy` names them).  The caller has
+    synchronised the device."""
+    arrays = {"obs": venv.obs_d.cpu().numpy().astype(np.float32, copy=False),
+              "reward": venv.reward_d.cpu().numpy().astype(np.float64, copy=False),
+              "done": venv.done_d.cpu().numpy().astype(np.float32),
+              "day_return": venv.return_d.cpu().numpy().astype(np.float64, copy=False)}
+    E = venv.num_envs
+    row_bytes = sum(a.nbytes for a in arrays.values()) // E + 8   # + the env id
+    if row_bytes * E > DUMP_LIMIT_BYTES:
+        ids = np.sort(np.random.default_rng(seed).choice(E, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        arrays = {k: a[ids] for k, a in arrays.items()}
+        arrays["env_ids"] = ids.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -232,7 +265,7 @@ def launch_ranks(args, kw):
         print(f"bench.py: --gpus {args.gpus} needs {args.gpus} visible GPUs for RCCL (one rank per GPU); "
               f"{ndev} visible (--dist-backend gloo shares them)", file=sys.stderr)
         return 2
-    cpu = None if args.no_cpu_baseline else cpu_baseline(kw, args.cpu_budget)
+    cpu = cpu_baseline(kw, args.cpu_budget) if args.full and not args.no_cpu_baseline else None
     with tempfile.NamedTemporaryFile("w", suffix=".json", prefix="sng_cpu_baseline_", delete=False) as fp:
         json.dump(cpu, fp)
         cpu_file = fp.name
@@ -259,7 +292,12 @@ def main():
     ap.add_argument("--lanes", type=int, default=0, help="step kernel lanes per env (0 = library default)")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline and the roofline figures "
+                         "(per-kernel timing of eager days, copy-probe ceilings, committed rocprofv3 summaries)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed day's outputs (obs, reward, done, day_return) as DIR/<name>.npy")
     ap.add_argument("--timing-days", type=int, default=3, help="eager days for the per-kernel HIP-event probe")
     ap.add_argument("--graph-days", type=int, default=20, help="days per graph replay (divides steps)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -297,7 +335,7 @@ def main():
     # the CPU baseline is rank 0's report, measured before the GPU is initialised (forked workers, host
     # cores otherwise idle); under bench.py's own launcher the parent measured it before starting the ranks
     cpu, launcher = None, os.environ.get("SNG_BENCH_LAUNCHER", "external" if env_world else "none (N = 1)")
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if os.environ.get("SNG_BENCH_CPU_BASELINE"):
             with open(os.environ["SNG_BENCH_CPU_BASELINE"]) as fp:
                 cpu = json.load(fp)
@@ -399,13 +437,16 @@ def main():
     # isolated per-dispatch step time come from HIP start/stop events attached to each dispatch
     # (hipExtLaunchKernel) over eager days of the same env/actions, right after the timed region.
     day_gpu_us = ev0.elapsed_time(ev1) * 1e3 / args.steps
-    kernel_ms, reset_ms = venv.time_step_kernels(acts, days=args.timing_days, with_resets=True)
-    reset_us = float(np.mean(reset_ms)) * 1e3
-    graph_step_us = (day_gpu_us - reset_us) / T
-    timing_src = (f"in-graph: (HIP-event device time per timed day {day_gpu_us:.2f} us - reset kernel "
-                  f"{reset_us:.2f} us) / {T} step dispatches; reset and eager_launch_us from HIP start/stop "
-                  f"events on each dispatch (hipExtLaunchKernel), {args.timing_days} eager days after the "
-                  f"timed region, same stream/env/actions")
+    if args.dump_outputs and rank == 0:   # before anything else steps the env
+        dump_outputs(args.dump_outputs, venv, args.seed)
+    if args.full:
+        kernel_ms, reset_ms = venv.time_step_kernels(acts, days=args.timing_days, with_resets=True)
+        reset_us = float(np.mean(reset_ms)) * 1e3
+        graph_step_us = (day_gpu_us - reset_us) / T
+        timing_src = (f"in-graph: (HIP-event device time per timed day {day_gpu_us:.2f} us - reset kernel "
+                      f"{reset_us:.2f} us) / {T} step dispatches; reset and eager_launch_us from HIP start/stop "
+                      f"events on each dispatch (hipExtLaunchKernel), {args.timing_days} eager days after the "
+                      f"timed region, same stream/env/actions")
     elapsed = max_over_ranks(elapsed, device=coll_dev)
     # sanity: a day's returns are finite and <= 0
     ret = venv.return_d.cpu().numpy()
@@ -415,9 +456,8 @@ def main():
             got = xch.gathered(k).cpu().numpy()
             assert got.shape == (D, world * E) and np.isfinite(got).all() and (got <= 0).all() and (got < 0).any()
 
-    if rank == 0:
-        env_steps = world * E * T * args.steps
-        value = env_steps / elapsed
+    roof = None
+    if rank == 0 and args.full:
         launch_s = graph_step_us * 1e-6
         eager_s = float(np.mean(kernel_ms)) * 1e-3
         bpl = survey_bytes(N) * E
@@ -459,6 +499,9 @@ def main():
                 "rocprof_avg_us": rp_us, "rocprof_file": rp_file,
                 "frac_rocprof": None if rp_us is None else frac(bpl, rp_us * 1e-6),
                 "frac_layout_rocprof": None if rp_us is None else frac(lpl, rp_us * 1e-6)}
+    if rank == 0:
+        env_steps = world * E * T * args.steps
+        value = env_steps / elapsed
         headline = (N == 10 and T == 24 and not noise and not args.v2x)
         metric = METRIC if headline else f"env-steps/sec (whole node) at N={E:,} envs × {N} chargers, {T}-step day"
         desc = ("v2x-" if args.v2x else "") + f"b-pv bounded sparse {args.time_interval}" + (

@@ -6,7 +6,8 @@ on the GPU box).  Only file paths and line counts are stored -- no reference tex
 Also tests/golden/reference_identifiers.json, for checking citations by content: per file, per line,
 the 8-hex-digit SHA-1 prefixes of the identifiers on it that contain an underscore or a lower-upper
 case change (`load_initial_values`, `SmartNanogridEnv`), and the line span of every class by the hash
-of its name.  Hashes only: no reference text is stored.
+of its name.  Hashes only: no reference text is stored.  tests/golden/reference_fixture_digests.json records
+the SHA-256 of both fixtures' content.
 
 Usage:  python tests/golden/make_line_counts.py
 """
@@ -47,7 +48,17 @@ def main():
         idents[rel] = {"lines": per_line, "classes": classes}
     with open(os.path.join(HERE, "reference_identifiers.json"), "w") as fp:
         json.dump(idents, fp, separators=(",", ":"))
+    # what tests/test_citations.py holds the two fixtures to where the reference tree is not at hand
+    digests = {"reference_line_counts.json": fixture_digest(dict(sorted(counts.items()))),
+               "reference_identifiers.json": fixture_digest(idents)}
+    with open(os.path.join(HERE, "reference_fixture_digests.json"), "w") as fp:
+        json.dump(digests, fp, indent=1)
     print(f"{len(counts)} files")
+
+
+def fixture_digest(obj):
+    """SHA-256 of a fixture's content (its JSON in canonical form, so the file's layout does not matter)."""
+    return hashlib.sha256(json.dumps(obj, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
 
 
 IDENT = re.compile(r"[A-Za-z_][A-Za-z0-9_]*")

@@ -16,8 +16,6 @@ import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 SOURCES = ["include", "smart-nanogrid-gym_amd/csrc", "smart-nanogrid-gym_amd/smart_nanogrid_gym", "oracle",
@@ -139,11 +137,36 @@ def test_reference_citations_resolve():
     assert not bad, "\n".join(bad)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only in the build container")
+def fixture_digest(obj):
+    """SHA-256 of a fixture's content (its JSON in canonical form, so the file's layout does not matter)."""
+    return hashlib.sha256(json.dumps(obj, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+def recorded_digest(name):
+    """What make_line_counts.py recorded for the fixture when it derived it from the reference."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_fixture_digests.json")) as fp:
+        return json.load(fp)[name]
+
+
+def reference_identifiers():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_identifiers.json")) as fp:
+        return json.load(fp)
+
+
 def test_line_counts_fixture_is_current():
-    for rel, n in reference_counts().items():
-        with open(os.path.join(REF, rel), "rb") as fp:
-            assert len(fp.read().splitlines()) == n, rel
+    """The fixture is the one make_line_counts.py derived from the reference (its recorded digest) and agrees
+    with the identifiers fixture, derived separately, file for file; where the reference tree is at hand, its
+    files are counted directly as well."""
+    counts = reference_counts()
+    assert fixture_digest(counts) == recorded_digest("reference_line_counts.json")
+    idents = reference_identifiers()
+    assert sorted(counts) == sorted(idents)
+    for rel, n in counts.items():
+        assert len(idents[rel]["lines"]) == n, rel
+    if os.path.isdir(REF):
+        for rel, n in counts.items():
+            with open(os.path.join(REF, rel), "rb") as fp:
+                assert len(fp.read().splitlines()) == n, rel
 
 
 def test_reference_citations_hold_their_identifiers():
@@ -186,11 +209,17 @@ def test_reference_citations_hold_their_identifiers():
     assert used == set(CONTENT_EXCEPTIONS), sorted(set(CONTENT_EXCEPTIONS) - used)   # no stale exceptions
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only in the build container")
 def test_identifiers_fixture_is_current():
-    with open(os.path.join(ROOT, "tests", "golden", "reference_identifiers.json")) as fp:
-        idents = json.load(fp)
+    """The fixture is the one make_line_counts.py derived from the reference (its recorded digest), every line
+    holds sorted 8-hex-digit hashes and every class span lies inside its file; where the reference tree is at
+    hand, its lines are hashed directly as well."""
+    idents = reference_identifiers()
+    assert fixture_digest(idents) == recorded_digest("reference_identifiers.json")
     for rel, d in idents.items():
-        with open(os.path.join(REF, rel), encoding="utf-8", errors="replace") as fp:
-            lines = fp.read().splitlines()
-        assert [sorted({ident_hash(t) for t in IDENT.findall(ln) if strong(t)}) for ln in lines] == d["lines"], rel
+        assert all(ids == sorted(set(ids)) and all(re.fullmatch(r"[0-9a-f]{8}", h) for h in ids) for ids in d["lines"]), rel
+        assert all(1 <= lo <= hi <= len(d["lines"]) for lo, hi in d["classes"].values()), rel
+    if os.path.isdir(REF):
+        for rel, d in idents.items():
+            with open(os.path.join(REF, rel), encoding="utf-8", errors="replace") as fp:
+                lines = fp.read().splitlines()
+            assert [sorted({ident_hash(t) for t in IDENT.findall(ln) if strong(t)}) for ln in lines] == d["lines"], rel

@@ -143,7 +143,7 @@ def test_bench_gpus2_launches_its_own_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--envs", "4096", "--dist-backend", "gloo", "--cpu-budget", "1", "--timing-days", "1"]
+           "--envs", "4096", "--dist-backend", "gloo", "--full", "--cpu-budget", "1", "--timing-days", "1"]
     env = dict(os.environ, SNG_CPU_BASELINE_PROCS="2")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, env=env)

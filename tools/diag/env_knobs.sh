@@ -1,10 +1,10 @@
 #!/bin/bash
 # HIP runtime knobs against the headline day (never changes the library): each configuration runs the bench
-# twice, interleaved, under its own time limit; the JSON lines land in gpurun_out/knobs/<name>_<i>.log.
+# twice, interleaved, under its own time limit; the JSON lines land in $OUT/knobs/<name>_<i>.log.
 # ROC_SYSTEM_SCOPE_SIGNAL=0 is left out: its bench hung until its time limit (profiles/r06_ab_hip_env_knobs.txt).
 #   tools/gpu ... -- 'bash tools/diag/env_knobs.sh'
 set -uo pipefail
-mkdir -p gpurun_out/knobs
+export OUT=${OUT:-diag_out}; mkdir -p "$OUT/knobs"
 configs=(
   "base:"
   "pc0:DEBUG_CLR_GRAPH_PACKET_CAPTURE=0"
@@ -19,9 +19,9 @@ for i in 1 2; do
   for c in "${configs[@]}"; do
     name=${c%%:*}; kv=${c#*:}
     if [ -n "$kv" ]; then
-      env "$kv" timeout -k 10 120 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > "gpurun_out/knobs/${name}_$i.log" 2>&1
+      env "$kv" timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/knobs/${name}_$i.log" 2>&1
     else
-      timeout -k 10 120 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > "gpurun_out/knobs/${name}_$i.log" 2>&1
+      timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/knobs/${name}_$i.log" 2>&1
     fi
     rc=$?
     echo "$name $i rc=$rc"
@@ -31,7 +31,7 @@ done
 python - <<'PY'
 import glob, json, os
 rows = {}
-for f in sorted(glob.glob("gpurun_out/knobs/*.log")):
+for f in sorted(glob.glob(os.path.join(os.environ["OUT"], "knobs", "*.log"))):
     name = os.path.basename(f)[:-4].rsplit("_", 1)[0]
     for line in open(f):
         if line.startswith("{"):

@@ -8,7 +8,7 @@ writes profiles/<tag>_kernel_stats.csv, profiles/<tag>_pmc.csv and an entry of
 profiles/pmc_step_kernel.json; the same for config 5 from prof_cfg5/, pmc5_fetch/ and pmc5_write/
 (profiles/<tag>_kernel_stats_config5.csv, profiles/<tag>_pmc_config5.csv).  Every entry carries the build id of
 the library measured (<out>/build_id.txt, written by tools/gpu_session.sh; sng_build_id()), and the rocprof
-summaries are listed with theirs in profiles/kernel_stats_index.json: bench.py quotes only measurements of the
+summaries are listed with theirs in profiles/kernel_stats_index.json: bench.py --full quotes only measurements of the
 build it runs.
 
 HBM bytes per launch (MI355X_MICROARCH.md, HBM section): FETCH_SIZE and WRITE_SIZE are in KiB;

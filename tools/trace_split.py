@@ -1,5 +1,5 @@
 """Split a rocprofv3 kernel trace (`--kernel-trace --output-format csv`, *_kernel_trace.csv) of
-`bench.py` into the step kernel's dispatches inside graph replays (back-to-back behind the previous
+`bench.py --full` into the step kernel's dispatches inside graph replays (back-to-back behind the previous
 node) and the eager HIP-event probe days, and by timestep within the day.
 
     python tools/trace_split.py gpurun_out/prof [kernel-substring]
