@@ -51,10 +51,10 @@ typedef enum SngPenaltyMode {
 
 /* How sng_reset draws the new day's vehicles. */
 typedef enum SngRngMode {
-    /* Host MT19937 streams identical to the reference's global RNGs: environment i
+    /* MT19937 streams identical to the reference's global RNGs: environment i
      * reproduces `np.random.seed(seed + i); random.seed(seed + i)` followed by the
      * reference's reset()/step() sequence (charging_station.py:200-279,
-     * smart_nanogrid_environment.py:181,349).  Generated on the host CPU threads. */
+     * smart_nanogrid_environment.py:181,349).  The streams live and are drawn on the device. */
     SNG_RNG_REFERENCE = 0,
     /* Counter-based hash streams on the GPU: same distributions, different draws (the arrival
      * SoC is drawn as a float32 value).  Fully device-resident; graph-capturable.  Each device
@@ -202,9 +202,11 @@ int sng_set_env_offset(SngEnv *env, int64_t offset);
 
 /* SmartNanogridEnv.reset() (smart_nanogrid_environment.py:311-351) with generate_new_initial_values=True:
  * a new day for every env (charging_station.py:152-186), timestep 0, the t=0 observation into
- * obs[num_envs][obs_dim].  SNG_RNG_REFERENCE builds the days on host threads (the CPUs of
- * sched_getaffinity, capped by SNG_HOST_THREADS / OMP_NUM_THREADS) and uploads each chunk of envs
- * while the next is built. */
+ * obs[num_envs][obs_dim].  SNG_RNG_REFERENCE draws the days on the device too: numpy's and Python's
+ * MT19937 stream of every env live there (ref_day2_kernel draws a day, the t = 0 observation's kernel the
+ * PV ratio), and the next day's stream blocks are prepared on a side stream while this day is stepped.  Host
+ * threads (the CPUs of sched_getaffinity, capped by SNG_HOST_THREADS / OMP_NUM_THREADS) only seed Python's
+ * streams, once per seeding, and encode the injected days of sng_reset_from_scenario. */
 int sng_reset(SngEnv *env, int rng_mode, float *obs, void *stream);
 
 /* reset(generate_new_initial_values=False) (smart_nanogrid_environment.py:347-357): replays the day this

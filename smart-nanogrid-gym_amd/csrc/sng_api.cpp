@@ -2,9 +2,10 @@
 //
 // Owns the per-handle device state, builds the constant tables, turns days in the
 // reference's own layout (25-slot arrays + arrival/departure lists) into the packed
-// per-charger-step words the step kernel reads, generates reference-exact days on host
-// threads (MT19937 streams) while uploading them, replays the last generated day, saves and
-// restores the whole simulation state, and captures whole days into hipGraphs.
+// per-charger-step words the step kernel reads, queues the device kernels that generate a day
+// (the device generator, or the reference's numpy and Python MT19937 streams drawn on the device:
+// host threads only seed Python's streams and encode injected days), replays the last generated
+// day, saves and restores the whole simulation state, and captures whole days into hipGraphs.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
@@ -12,6 +13,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,38 +24,16 @@
 #include <vector>
 
 #include "sng.h"
+#include "sng_device_scope.h"
+#include "sng_launch.h"
 #include "sng_layout.h"
 #include "sng_mt.h"
-
-namespace sng {
-hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
-                       const float *act, float *obs,
-                       double *reward, uint8_t *done, int64_t E, int t, int vec_io, hipStream_t stream,
-                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
-                           int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
-                           int py = 0);
-hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4, int i10, int i1,
-                           float *obs, double *ep_return, int vec_io,
-                           hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
-hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream);
-hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,
-                             hipEvent_t b);
-hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipStream_t stream);
-hipError_t launch_mt_prepare(const RefStreams &rs, int64_t E, hipStream_t stream);
-hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStreams &rs, int64_t E, int i4, int i10,
-                          int i1, bool prepare, hipStream_t stream);
-int step_lanes_supported(int n, int lanes);
-int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);
-}  // namespace sng
 
 using namespace sng;
 
 namespace {
 
 thread_local std::string g_create_error;
-
 
 // numpy pairwise_sum (contiguous float64), used by ndarray.mean() in
 // PVSystemManager.calculate_solar_irradiance_mean (pv_system_manager.py:34-44)
@@ -502,8 +482,8 @@ struct SngEnv {
     uint32_t *h_word = nullptr;
     double *h_aux = nullptr, *h_req = nullptr, *h_ratio = nullptr, *h_pen0 = nullptr;
     hipEvent_t staging_done = nullptr;
-    // reference RNG streams of every env (allocated on first use): numpy's on the device (RefStreams,
-    // drawn by ref_day_kernel), Python's on the host (two or three draws a day)
+    // reference RNG streams of every env (allocated on first use), both on the device: numpy's (rs, drawn by
+    // ref_day2_kernel) and Python's (ps below: two or three draws a day, seeded on host threads)
     RefStreams rs{};
     bool np_seeded = false;
     // the next day's stream blocks are prepared (mt_prepare_kernel) on a side stream while a day is stepped;
@@ -527,14 +507,33 @@ struct SngEnv {
 };
 
 // The Params fields that say how the loaded day is encoded and stepped; a steps-only graph
-// captures them and may replay only over a day with the same key.
+// captures them and may replay only over a day with the same key.  Nothing else writes those four fields:
+// a day kind below makes the key, load_day / with_day put it into a Params.  (Four int32 and no constructor:
+// the checkpoint header stores the key as it is.)
 struct DayKey {
     int32_t packed, req_stream, req_zero, bump_day;
     bool operator==(const DayKey &o) const {
         return packed == o.packed && req_stream == o.req_stream && req_zero == o.req_zero && bump_day == o.bump_day;
     }
+    static DayKey of(const Params &p) { return DayKey{p.packed, p.req_stream, p.req_zero, p.bump_day}; }
+    // a device-RNG day: the generator writes packed records (sng_layout.h); the day owns a day-counter value,
+    // which its first step advances
+    static DayKey device_day(const Params &p) { return DayKey{1, p.req_enabled, 0, 1}; }
+    // a reference-RNG or injected day: word + f64 aux planes, with or without the requested-SoC stream
+    static DayKey host_day(bool req_stream) { return DayKey{0, req_stream ? 1 : 0, 0, 0}; }
+    // the loaded day replayed: Requested_SOC reads 0 and the steps do not count the day again
+    DayKey replayed() const { return DayKey{packed, req_stream, 1, 0}; }
+    // sng_set_seed: the day counter restarts, so an unstepped device day no longer owns day 0
+    DayKey disowned() const { return DayKey{packed, req_stream, req_zero, 0}; }
+    bool unstepped_device_day(int t) const { return packed && bump_day && t == 0; }
 };
-static DayKey day_key(const Params &p) { return DayKey{p.packed, p.req_stream, p.req_zero, p.bump_day}; }
+static Params with_day(Params p, const DayKey &k) {
+    p.packed = k.packed;
+    p.req_stream = k.req_stream;
+    p.req_zero = k.req_zero;
+    p.bump_day = k.bump_day;
+    return p;
+}
 
 struct SngGraph {
     SngEnv *env = nullptr;
@@ -569,8 +568,52 @@ int hip_fail(SngEnv *env, hipError_t e, const char *what) {
         hipError_t _e = (expr);                              \
         if (_e != hipSuccess) return hip_fail(env, _e, #expr); \
     } while (0)
+// ... and of a helper that returns an SNG_* code and has set the handle's error itself
+#define SNG_TRY(expr)                     \
+    do {                                  \
+        if (int _rc = (expr)) return _rc; \
+    } while (0)
+
+// An entry point's prologue, after its argument checks: the rest of the call runs on the handle's device (DeviceScope).
+// A declaration and a statement that may return: once per function, at block scope, never under a brace-less `if`.
+#define ON_DEVICE_OF(env)               \
+    DeviceScope dev_((env)->device);    \
+    HIP_TRY(env, dev_.err)
 
 bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+
+// --- the loaded day (DayKey, t, day_finished, gen_mode, gen_loaded) ---
+void load_day(SngEnv *env, const DayKey &k) { env->p = with_day(env->p, k); }
+// a day begins: its t = 0 observation is queued
+void begin_day(SngEnv *env) {
+    env->t = 0;
+    env->day_finished = false;
+}
+// a generated day is now the one reset(generate_new_initial_values=False) replays
+void generated_day_loaded(SngEnv *env, int rng_mode) {
+    env->gen_mode = rng_mode;
+    env->gen_loaded = true;
+}
+// whole days ran (a day graph, the timed days): the last one is over
+void days_ran(SngEnv *env) {
+    env->t = env->p.T;
+    env->day_finished = true;
+}
+// A device day is counted by its first step (step_kernel advances the day counter); one that was reset but
+// never stepped is counted here, before what follows it, so the next device day drawn is a new one.
+hipError_t count_unstepped_device_day(SngEnv *env, hipStream_t st) {
+    return DayKey::of(env->p).unstepped_device_day(env->t) ? launch_bump_day(env->ds, st) : hipSuccess;
+}
+// sng_step / sng_step_host: the loaded day has a step left; and that step was queued
+int step_begin(SngEnv *env) {
+    if (env->t < 0) return fail(env, SNG_ERR_STATE, "step() before reset()");
+    if (env->t >= env->p.T) return fail(env, SNG_ERR_STATE, "the day is over: call reset()");
+    return SNG_OK;
+}
+void step_queued(SngEnv *env) {
+    env->t += 1;
+    if (env->t == env->p.T) env->day_finished = true;
+}
 
 InfoPtrs info_ptrs(const SngInfo *i) {
     InfoPtrs o{};
@@ -616,12 +659,23 @@ int ensure_staging(SngEnv *env, bool with_req) {
     return SNG_OK;
 }
 
+// Orders `st` after the side stream's preparation of the streams (sng_reset), before st touches them.
+int await_prepare(SngEnv *env, hipStream_t st) {
+    if (env->prep_launched) HIP_TRY(env, hipStreamWaitEvent(st, env->prep_done, 0));
+    return SNG_OK;
+}
+// one stream set's device blocks ([E][2][624] words and the positions), on first use
+int alloc_streams(SngEnv *env, RefStreams &r) {
+    if (r.mt) return SNG_OK;
+    HIP_TRY(env, hipMalloc(&r.mt, (size_t)env->E * 2 * kMtN * sizeof(uint32_t)));
+    HIP_TRY(env, hipMalloc(&r.pos, (size_t)env->E * sizeof(int32_t)));
+    return SNG_OK;
+}
 // The reference's global RNG streams of every env, np.random.seed(s) and random.seed(s) with
 // s = seed + global env index (SngRngMode SNG_RNG_REFERENCE), both on the device.  Python's is seeded on
 // the host threads (CPython's init_by_array, sng_mt.h) and uploaded once into the RefStreams layout
 // (block 0, position N: the first draw twists), then drawn by observe0_kernel (py_ratio_lane): random.randint(0, 180)
 // for a reset's PV ratio, after the day-end draw the last step owes (smart_nanogrid_environment.py:181, 349).
-int await_prepare(SngEnv *env, hipStream_t st);
 // numpy's np.random.seed takes seeds in [0, 2^32): env i of a reference-RNG population is seeded
 // seed + env offset + i, so the last env's seed must stay below 2^32 (mt_seed_kernel would wrap it).
 int check_reference_seed(SngEnv *env) {
@@ -635,14 +689,10 @@ int check_reference_seed(SngEnv *env) {
 
 int ensure_py_streams(SngEnv *env, hipStream_t st) {
     const size_t E = (size_t)env->E;
-    if (int rc = check_reference_seed(env)) return rc;
-    if (!env->ps.mt) {
-        HIP_TRY(env, hipMalloc(&env->ps.mt, E * 2 * kMtN * sizeof(uint32_t)));
-        HIP_TRY(env, hipMalloc(&env->ps.pos, E * sizeof(int32_t)));
-    }
+    SNG_TRY(check_reference_seed(env));
+    SNG_TRY(alloc_streams(env, env->ps));
     if (env->py_seeded) return SNG_OK;
-    int rc = await_prepare(env, st);   // no preparation may still be writing the streams
-    if (rc) return rc;
+    SNG_TRY(await_prepare(env, st));   // no preparation may still be writing the streams
     std::vector<uint32_t> words(E * kMtN);
     std::vector<int32_t> pos(E);
     const uint64_t s0 = env->seed + (uint64_t)env->p.env_offset;
@@ -666,22 +716,12 @@ int ensure_py_streams(SngEnv *env, hipStream_t st) {
     return SNG_OK;
 }
 
-// Orders `st` after the side stream's preparation of the streams (sng_reset), before st touches them.
-int await_prepare(SngEnv *env, hipStream_t st) {
-    if (env->prep_launched) HIP_TRY(env, hipStreamWaitEvent(st, env->prep_done, 0));
-    return SNG_OK;
-}
-
 // ... and numpy's on the device (mt_seed_kernel), queued on `st`.
 int ensure_np_streams(SngEnv *env, hipStream_t st) {
-    if (int rc = check_reference_seed(env)) return rc;
-    if (!env->rs.mt) {
-        HIP_TRY(env, hipMalloc(&env->rs.mt, (size_t)env->E * 2 * kMtN * sizeof(uint32_t)));
-        HIP_TRY(env, hipMalloc(&env->rs.pos, (size_t)env->E * sizeof(int32_t)));
-    }
+    SNG_TRY(check_reference_seed(env));
+    SNG_TRY(alloc_streams(env, env->rs));
     if (!env->np_seeded) {
-        int rc = await_prepare(env, st);
-        if (rc) return rc;
+        SNG_TRY(await_prepare(env, st));
         HIP_TRY(env, launch_ref_seed(env->rs, env->seed + (uint64_t)env->p.env_offset, env->E, st));
         env->np_seeded = true;
         env->prepared = false;   // fresh streams: the first day prepares its blocks inline
@@ -689,25 +729,10 @@ int ensure_np_streams(SngEnv *env, hipStream_t st) {
     return SNG_OK;
 }
 
-// Per-thread scratch for one env's day in the reference layout.
-struct DayScratch {
-    std::vector<double> soc, occ, cap, req;
-    std::vector<int32_t> arr, dep;
-    DayView view(int N, int S, int V) {
-        soc.assign((size_t)N * S, 0.0);
-        occ.assign((size_t)N * S, 0.0);
-        cap.assign((size_t)N * S, 0.0);
-        req.assign((size_t)N * S, 0.0);
-        arr.assign((size_t)N * V, -1);
-        dep.assign((size_t)N * V, -1);
-        return DayView{soc.data(), occ.data(), cap.data(), req.data(), arr.data(), dep.data(), V, S};
-    }
-};
-
 // Build every env's day on host threads and upload it while the rest is still being built:
 // workers take chunks of envs and encode them into the pinned [T][N][E] staging planes; as soon as
 // chunk k (in order) is encoded, this thread enqueues its columns of the planes as one 2D copy per
-// plane.  build(i, scratch, need_req, err) builds env i.  req_upload: the requested-SoC plane goes
+// plane.  build(i, need_req, err) builds env i.  req_upload: the requested-SoC plane goes
 // up with the chunks (1), after the last chunk if any env needs it (-1: decided by need_req), or
 // not at all (0).  Returns SNG_OK or an error; *need_req_out reports whether any env needed it.
 template <class Build>
@@ -725,7 +750,6 @@ int build_and_upload(SngEnv *env, int req_upload, hipStream_t st, bool *need_req
     std::atomic<int64_t> next{0};
     std::atomic<bool> stop{false}, need_req{false};
     auto worker = [&]() {
-        DayScratch scratch;
         for (;;) {
             const int64_t k = next.fetch_add(1);
             if (k >= nchunks) return;
@@ -738,7 +762,7 @@ int build_and_upload(SngEnv *env, int req_upload, hipStream_t st, bool *need_req
             } else {
                 const int64_t b = k * chunk, en = std::min(E, b + chunk);
                 for (int64_t i = b; i < en; ++i)
-                    if (!build(i, scratch, &nr, e)) {
+                    if (!build(i, &nr, e)) {
                         st_k = 2;
                         stop.store(true);
                         break;
@@ -801,20 +825,13 @@ int build_and_upload(SngEnv *env, int req_upload, hipStream_t st, bool *need_req
 int finish_host_day(SngEnv *env, bool req_stream, float *obs, hipStream_t st, int py_end, int py_draw) {
     HIP_TRY(env, hipMemcpyAsync(env->ds.ratio, env->h_ratio, env->E * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(env, hipMemcpyAsync(env->ds.pen0, env->h_pen0, env->E * sizeof(double), hipMemcpyHostToDevice, st));
-    if (py_end || py_draw) {   // the draws themselves run inside observe0_kernel below
-        int rc = await_prepare(env, st);
-        if (rc) return rc;
-    }
+    if (py_end || py_draw) SNG_TRY(await_prepare(env, st));   // the draws themselves run inside observe0_kernel below
     HIP_TRY(env, hipEventRecord(env->staging_done, st));
-    env->p.req_stream = req_stream ? 1 : 0;
-    env->p.packed = 0;   // word + f64 aux planes
-    env->p.req_zero = 0;
-    env->p.bump_day = 0;
+    load_day(env, DayKey::host_day(req_stream));
     HIP_TRY(env, sng::launch_profiles(env->p, env->ds, env->E, st));
     HIP_TRY(env, sng::launch_observe0(env->p, env->ds, obs, nullptr, env->E, aligned16(obs) ? 1 : 0, st, OBS0_HOST, -1,
                                       &env->ps, (py_draw ? 1 : 0) | (py_end ? 2 : 0)));
-    env->t = 0;
-    env->day_finished = false;
+    begin_day(env);
     return SNG_OK;
 }
 
@@ -936,7 +953,7 @@ int sng_create(const SngConfig *cfg, int device, int64_t num_envs, uint64_t seed
     p.penalty_mode = c.penalty_mode;
     p.diff_caps = c.different_vehicle_capacities ? 1 : 0;
     p.req_enabled = c.requested_state_of_charge ? 1 : 0;
-    p.req_stream = p.req_enabled;
+    p = with_day(p, DayKey::host_day(p.req_enabled != 0));   // before the first reset: no day is loaded
     p.obs_dim = (1 + p.pv) * 4 + 2 * p.n + p.bess;   // smart_nanogrid_environment.py:90-96
     p.act_dim = p.n + p.bess;                          // :101-118
     p.dt = c.time_interval_hours;
@@ -997,10 +1014,10 @@ int sng_create(const SngConfig *cfg, int device, int64_t num_envs, uint64_t seed
     // checkpoint fingerprint: every configuration scalar that changes the simulation, and the tables
     env->cfg_hash = fnv1a(&ht, sizeof ht, config_fingerprint(c));
 
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) {
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) {
         delete env;
-        return fail(nullptr, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        return fail(nullptr, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev.err));
     }
     auto alloc = [&](void **ptr, size_t bytes) -> bool {
         hipError_t r = hipMalloc(ptr, bytes);
@@ -1047,7 +1064,7 @@ int sng_create(const SngConfig *cfg, int device, int64_t num_envs, uint64_t seed
 
 void sng_destroy(SngEnv *env) {
     if (!env) return;
-    (void)hipSetDevice(env->device);
+    DeviceScope scope(env->device);
     if (env->prep_stream) {
         (void)hipStreamSynchronize(env->prep_stream);
         (void)hipStreamDestroy(env->prep_stream);
@@ -1092,7 +1109,7 @@ int sng_set_env_offset(SngEnv *env, int64_t offset) {
 
 int sng_set_seed(SngEnv *env, uint64_t seed, void *stream) {
     if (!env) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null handle");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     env->seed = seed;
     env->p.seed = seed;
     env->np_seeded = false;   // re-seeded (seed + offset + i) at the next reset
@@ -1101,35 +1118,25 @@ int sng_set_seed(SngEnv *env, uint64_t seed, void *stream) {
     env->replays = 0;
     // device days restart at day 0 of the new streams; the loaded day stays loaded
     HIP_TRY(env, hipMemsetAsync(env->ds.episode, 0, sizeof(uint64_t), as_stream(stream)));
-    if (env->p.packed && env->t == 0) env->p.bump_day = 0;   // an unstepped device day no longer owns day 0
+    if (DayKey::of(env->p).unstepped_device_day(env->t)) load_day(env, DayKey::of(env->p).disowned());
     HIP_TRY(env, hipStreamSynchronize(as_stream(stream)));
     return SNG_OK;
 }
 
 int sng_reset(SngEnv *env, int rng_mode, float *obs, void *stream) {
     if (!env || !obs) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     if (rng_mode == SNG_RNG_DEVICE) {
         if (!device_rng_ok(env)) return fail(env, SNG_ERR_UNSUPPORTED, "device RNG needs time_interval <= 2h");
-        const bool unstepped_device_day = env->p.packed && env->p.bump_day && env->t == 0;
-        env->p.req_stream = env->p.req_enabled;
-        env->p.packed = 1;   // the generator writes packed records (sng_layout.h)
-        env->p.req_zero = 0;
-        env->p.bump_day = 1;
-        if (env->p.req_stream) {
-            int rc = ensure_req(env);
-            if (rc) return rc;
-        }
-        // a device day's first step advances the day counter (step_kernel); a second device reset
-        // with no step in between advances it here, so it still draws a new day
-        if (unstepped_device_day) HIP_TRY(env, launch_bump_day(env->ds, st));
+        if (env->p.req_enabled) SNG_TRY(ensure_req(env));
+        // a second device reset with no step in between still draws a new day
+        HIP_TRY(env, count_unstepped_device_day(env, st));
+        load_day(env, DayKey::device_day(env->p));
         HIP_TRY(env, launch_generate(env->p, env->ds, env->seed, env->E, env->i4, env->i10, env->i1, obs, nullptr,
                                      aligned16(obs) ? 1 : 0, st));
-        env->t = 0;
-        env->day_finished = false;
-        env->gen_mode = SNG_RNG_DEVICE;
-        env->gen_loaded = true;
+        begin_day(env);
+        generated_day_loaded(env, SNG_RNG_DEVICE);
         return SNG_OK;
     }
     if (rng_mode != SNG_RNG_REFERENCE) return fail(env, SNG_ERR_INVALID_ARGUMENT, "unknown rng_mode");
@@ -1137,27 +1144,18 @@ int sng_reset(SngEnv *env, int rng_mode, float *obs, void *stream) {
     // the day on the device (ref_day2_kernel: numpy's stream, draw for draw), then the PV ratio from each
     // env's Python stream on the device, after the day-end draw the last step still owes
     // (smart_nanogrid_environment.py:181, 349)
-    int rc = ensure_np_streams(env, st);
-    if (rc) return rc;
-    rc = ensure_py_streams(env, st);
-    if (rc) return rc;
+    SNG_TRY(ensure_np_streams(env, st));
+    SNG_TRY(ensure_py_streams(env, st));
     const bool with_req = env->p.req_enabled != 0;
-    if (with_req) {
-        rc = ensure_req(env);
-        if (rc) return rc;
-    }
-    rc = await_prepare(env, st);
-    if (rc) return rc;
+    if (with_req) SNG_TRY(ensure_req(env));
+    SNG_TRY(await_prepare(env, st));
     if (!env->prep_stream) {
         HIP_TRY(env, hipStreamCreateWithFlags(&env->prep_stream, hipStreamNonBlocking));
         HIP_TRY(env, hipEventCreateWithFlags(&env->prep_done, hipEventDisableTiming));
         HIP_TRY(env, hipEventCreateWithFlags(&env->day_drawn, hipEventDisableTiming));
     }
-    env->p.req_stream = with_req ? 1 : 0;
+    load_day(env, DayKey::host_day(with_req));
     HIP_TRY(env, launch_ref_day(env->p, env->ds, env->rs, env->E, env->i4, env->i10, env->i1, !env->prepared, st));
-    env->p.packed = 0;   // word + f64 aux planes
-    env->p.req_zero = 0;
-    env->p.bump_day = 0;
     HIP_TRY(env, sng::launch_profiles(env->p, env->ds, env->E, st));
     // (the t = 0 penalty of a generated day is 0: observe0 writes it)
     // (the PV ratio from each env's Python stream, after the owed day-end draw, inside observe0_kernel)
@@ -1173,10 +1171,8 @@ int sng_reset(SngEnv *env, int rng_mode, float *obs, void *stream) {
     HIP_TRY(env, hipEventRecord(env->prep_done, env->prep_stream));
     env->prep_launched = true;
     env->prepared = true;
-    env->t = 0;
-    env->day_finished = false;
-    env->gen_mode = SNG_RNG_REFERENCE;
-    env->gen_loaded = true;
+    begin_day(env);
+    generated_day_loaded(env, SNG_RNG_REFERENCE);
     return SNG_OK;
 }
 
@@ -1188,33 +1184,27 @@ int sng_reset_replay(SngEnv *env, float *obs, void *stream) {
                                         "(initial_values.json, charging_station.py:185-186): none was generated yet"
                                       : "reset(generate_new_initial_values=False) replays the last generated day; an "
                                         "injected day (sng_reset_from_scenario) has replaced it since");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     const int vec = aligned16(obs) ? 1 : 0;
-    // a device day is counted by its first step; one replayed before any step was never counted, and
-    // the replay's steps do not count (bump_day = 0 below), so count it here, as sng_reset does for a
-    // second device reset in a row: the next device reset then draws a new day
-    if (env->p.packed && env->p.bump_day && env->t == 0) HIP_TRY(env, launch_bump_day(env->ds, st));
+    // a device day replayed before any step was never counted, and the replay's steps do not count it
+    // (DayKey::replayed), so count it here: the next device reset then draws a new day
+    HIP_TRY(env, count_unstepped_device_day(env, st));
     if (env->gen_mode == SNG_RNG_REFERENCE) {
         // a new random_pv_shift_ratio from each env's Python stream (smart_nanogrid_environment.py:349),
         // after the day-end draw the last step still owes (:181); the numpy stream is not touched
-        int rc = ensure_py_streams(env, st);
-        if (rc) return rc;
-        rc = await_prepare(env, st);
-        if (rc) return rc;
-        env->p.req_zero = 1;
-        env->p.bump_day = 0;
+        SNG_TRY(ensure_py_streams(env, st));
+        SNG_TRY(await_prepare(env, st));
+        load_day(env, DayKey::of(env->p).replayed());
         HIP_TRY(env, sng::launch_observe0(env->p, env->ds, obs, nullptr, env->E, vec, st, OBS0_REPLAY, -1, &env->ps,
                                           1 | (env->day_finished ? 2 : 0)));
     } else {
-        env->p.req_zero = 1;
-        env->p.bump_day = 0;
+        load_day(env, DayKey::of(env->p).replayed());
         HIP_TRY(env, sng::launch_observe0(env->p, env->ds, obs, nullptr, env->E, vec, st, OBS0_REPLAY,
                                           (int64_t)env->replays));
         env->replays += 1;
     }
-    env->t = 0;
-    env->day_finished = false;
+    begin_day(env);
     return SNG_OK;
 }
 
@@ -1226,29 +1216,22 @@ int sng_reset_from_scenario(SngEnv *env, const SngScenario *sc, float *obs, void
     if (!sc->soc || !sc->occupancy || !sc->capacity || !sc->requested_soc || !sc->arrivals || !sc->departures ||
         sc->max_vehicles < 1)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "incomplete scenario");
-    HIP_TRY(env, hipSetDevice(env->device));
-    int rc = ensure_staging(env, true);
-    if (rc) return rc;
+    ON_DEVICE_OF(env);
+    SNG_TRY(ensure_staging(env, true));
     // Python-stream accounting (env i == the reference seeded seed + i): the day-end draw the last
     // step still owes (smart_nanogrid_environment.py:181), and, when no ratio is given, the reset's own
     // draw (:349) -- what reset(generate_new_initial_values=False) consumes
     const bool draw_ratio = sc->pv_ratio == nullptr;
-    if (draw_ratio) {
-        rc = ensure_py_streams(env, as_stream(stream));
-        if (rc) return rc;
-    }
+    if (draw_ratio) SNG_TRY(ensure_py_streams(env, as_stream(stream)));
     const bool end_draw = env->day_finished && env->py_seeded;
     const int N = env->p.n, V = sc->max_vehicles, S = env->slots;
     // the requested-SoC plane goes up with the chunks when the config enables it (the step reads it
     // then), else only if some penalised slot of the given days is not 1.0
     const bool req_enabled = env->p.req_enabled != 0;
-    if (req_enabled) {
-        rc = ensure_req(env);
-        if (rc) return rc;
-    }
+    if (req_enabled) SNG_TRY(ensure_req(env));
     bool need = false;
-    rc = build_and_upload(env, req_enabled ? 1 : -1, as_stream(stream), &need,
-                          [&](int64_t i, DayScratch &, bool *nr, std::string &e) -> bool {
+    int rc = build_and_upload(env, req_enabled ? 1 : -1, as_stream(stream), &need,
+                          [&](int64_t i, bool *nr, std::string &e) -> bool {
                               const size_t o = (size_t)i * N * S, ol = (size_t)i * N * V;
                               DayView d{const_cast<double *>(sc->soc + o), const_cast<double *>(sc->occupancy + o),
                                         const_cast<double *>(sc->capacity + o),
@@ -1273,38 +1256,20 @@ int sng_reset_from_scenario(SngEnv *env, const SngScenario *sc, float *obs, void
         env->err += " (the loaded day was partly overwritten: reset again)";
         return rc;
     }
-    rc = finish_host_day(env, req_enabled || need, obs, as_stream(stream), end_draw ? 1 : 0, draw_ratio ? 1 : 0);
-    if (rc) return rc;
+    SNG_TRY(finish_host_day(env, req_enabled || need, obs, as_stream(stream), end_draw ? 1 : 0, draw_ratio ? 1 : 0));
     env->gen_loaded = false;   // the generated day a replay restores is no longer loaded
     return SNG_OK;
 }
 
-// The handle's device for the length of a call, the caller's current device restored after it (sng_step and
-// sng_step_host are called per step without a device guard of the caller's own).
-struct DeviceScope {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) err = hipSetDevice(d);
-    }
-    ~DeviceScope() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
 int sng_step(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done, const SngInfo *info,
              void *stream) {
     if (!env || !actions || !obs || !reward || !done) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
-    if (env->t < 0) return fail(env, SNG_ERR_STATE, "step() before reset()");
-    if (env->t >= env->p.T) return fail(env, SNG_ERR_STATE, "the day is over: call reset()");
-    DeviceScope dev(env->device);
-    HIP_TRY(env, dev.err);
+    SNG_TRY(step_begin(env));
+    ON_DEVICE_OF(env);
     const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
     HIP_TRY(env, launch_step(env->p, env->ds, info_ptrs(info), env->host_tab, actions, obs, reward, done, env->E, env->t, vec,
                              as_stream(stream)));
-    env->t += 1;
-    if (env->t == env->p.T) env->day_finished = true;
+    step_queued(env);
     return SNG_OK;
 }
 
@@ -1312,12 +1277,10 @@ int sng_step_host(SngEnv *env, const float *actions, float *obs, double *reward,
                   const SngInfo *info, void *stream) {
     if (!env || !actions || !obs || !reward || !done || !step_flags)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
-    if (env->t < 0) return fail(env, SNG_ERR_STATE, "step() before reset()");
-    if (env->t >= env->p.T) return fail(env, SNG_ERR_STATE, "the day is over: call reset()");
+    SNG_TRY(step_begin(env));
     if (info && info->flags)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "sng_step_host returns the step's flags itself: SngInfo.flags must be null");
-    DeviceScope dev(env->device);
-    HIP_TRY(env, dev.err);
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     const size_t E = (size_t)env->E, A = (size_t)env->p.act_dim, O = (size_t)env->p.obs_dim;
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -1339,8 +1302,7 @@ int sng_step_host(SngEnv *env, const float *actions, float *obs, double *reward,
     HIP_TRY(env, launch_step(env->p, env->ds, ip, env->host_tab, reinterpret_cast<const float *>(d),
                              reinterpret_cast<float *>(d + o_obs), reinterpret_cast<double *>(d + o_rew),
                              reinterpret_cast<uint8_t *>(d + o_done), env->E, env->t, 1, st));
-    env->t += 1;
-    if (env->t == env->p.T) env->day_finished = true;
+    step_queued(env);
     HIP_TRY(env, hipStreamSynchronize(st));
     std::memcpy(obs, h + o_obs, E * O * 4);
     std::memcpy(reward, h + o_rew, E * 8);
@@ -1357,7 +1319,7 @@ int sng_step_kernel_name(const SngEnv *env, const SngInfo *info, char *buf, int3
 
 int sng_read_errors(SngEnv *env, uint32_t *host_flags, int clear, void *stream) {
     if (!env || !host_flags) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     HIP_TRY(env, hipMemcpyAsync(host_flags, env->ds.flags, env->E * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (clear) HIP_TRY(env, hipMemsetAsync(env->ds.flags, 0, env->E * sizeof(uint32_t), st));
@@ -1370,7 +1332,7 @@ int sng_read_errors(SngEnv *env, uint32_t *host_flags, int clear, void *stream) 
 static int copy_env_array(SngEnv *env, double *dev, double *host, bool to_host, void *stream, const char *what) {
     if (!env) return SNG_ERR_INVALID_ARGUMENT;
     if (!host) return fail(env, SNG_ERR_INVALID_ARGUMENT, std::string(what) + ": null host array");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     if (to_host)
         HIP_TRY(env, hipMemcpyAsync(host, dev, env->E * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1396,7 +1358,7 @@ int sng_get_pv_ratio(SngEnv *env, double *h, void *stream) {
 int sng_get_vehicle_soc(SngEnv *env, double *h, void *stream) {
     if (!env) return SNG_ERR_INVALID_ARGUMENT;
     if (!h) return fail(env, SNG_ERR_INVALID_ARGUMENT, "sng_get_vehicle_soc: null host array");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     const int N = env->p.n;
     hipStream_t st = as_stream(stream);
     // charger pairs on the device (sng_layout.h soc_index) -> [E][N] on the host
@@ -1423,7 +1385,7 @@ int sng_get_vehicle_soc(SngEnv *env, double *h, void *stream) {
 int sng_set_vehicle_soc(SngEnv *env, const double *h, void *stream) {
     if (!env) return SNG_ERR_INVALID_ARGUMENT;
     if (!h) return fail(env, SNG_ERR_INVALID_ARGUMENT, "sng_set_vehicle_soc: null host array");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     const int N = env->p.n;
     std::vector<double> tmp((size_t)N * env->E);
     hipStream_t st = as_stream(stream);
@@ -1461,7 +1423,7 @@ int sng_get_scenario(SngEnv *env, int64_t first, int64_t count, int32_t V, doubl
     if (first < 0 || count < 1 || first + count > env->E || V < 1)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "env range or max_vehicles out of range");
     if (env->t < 0) return fail(env, SNG_ERR_STATE, "no day yet: call reset()");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     const int N = env->p.n, T = env->p.T, S = env->slots;
     const size_t rows = (size_t)T * N, pitch = (size_t)env->E, cnt = (size_t)count;
@@ -1580,26 +1542,41 @@ struct StateHeader {
     uint64_t config_hash, seed;
     int64_t env_offset;
     int32_t t, day_finished;
-    int32_t packed, req_stream, req_zero, bump_day;
+    DayKey day;   // packed, req_stream, req_zero, bump_day
     int32_t gen_mode, gen_loaded;
     uint64_t replays, day_counter;
     int32_t has_word, has_req, has_prof, has_return, has_streams, reserved;
     uint64_t total_bytes;
 };
+static_assert(sizeof(StateHeader) == 144 && offsetof(StateHeader, day) == 72 && sizeof(DayKey) == 16,
+              "the checkpoint header's bytes are format 5's");
 // the last byte is the checkpoint format version: '3' since the configuration fingerprint is hashed
 // field by field (round 3), '5' since the SoC state is stored in charger pairs, a day's stochastic profiles
 // as per-env keys and a device day's records in 2 B (round 4); a blob of another version is refused as such
 static const char kStateMagic[8] = {'S', 'N', 'G', 'S', 'T', 'A', 'T', '5'};
 
-// The blob's size for this handle and the header's section flags.
-static uint64_t state_bytes(const SngEnv *env, const StateHeader &h) {
+// The blob's device sections behind the header, in blob order, for this handle and the header's section flags:
+// sng_get_state pulls them, sng_set_state pushes them (the RNG streams follow, converted on the host).
+struct StateSection {
+    void *dev;
+    size_t bytes;
+};
+static std::vector<StateSection> state_sections(const SngEnv *env, const StateHeader &h, const double *ep_return) {
     const size_t E = (size_t)env->E, tl = env->timeline();
-    size_t b = sizeof(StateHeader) + (size_t)env->p.n * E * 8 + 4 * E * 8 + E * 4 + tl * 8;
-    if (h.has_word) b += tl * 4;
-    if (h.has_req) b += tl * 8;
-    if (h.has_prof) b += 2 * (size_t)E * 4;
-    if (h.has_return) b += E * 8;
-    if (h.has_streams) b += E * 2 * MT19937::kStateWords * 4;
+    const DeviceState &ds = env->ds;
+    std::vector<StateSection> s = {{ds.soc, (size_t)env->p.n * E * 8}, {ds.bess, E * 8}, {ds.bess0, E * 8},
+                                   {ds.ratio, E * 8}, {ds.pen0, E * 8}, {ds.flags, E * 4}};
+    if (h.has_word) s.push_back({ds.word, tl * 4});
+    s.push_back({ds.aux, tl * 8});
+    if (h.has_req) s.push_back({ds.req, tl * 8});
+    if (h.has_prof) s.push_back({ds.prof_key, 2 * E * 4});
+    if (h.has_return) s.push_back({const_cast<double *>(ep_return), E * 8});
+    return s;
+}
+
+static uint64_t state_bytes(const SngEnv *env, const StateHeader &h) {
+    size_t b = sizeof(StateHeader) + (h.has_streams ? (size_t)env->E * 2 * MT19937::kStateWords * 4 : 0);
+    for (const StateSection &s : state_sections(env, h, nullptr)) b += s.bytes;
     return b;
 }
 
@@ -1618,10 +1595,7 @@ static StateHeader state_layout(const SngEnv *env, bool with_return) {
     h.env_offset = env->p.env_offset;
     h.t = env->t;
     h.day_finished = env->day_finished ? 1 : 0;
-    h.packed = env->p.packed;
-    h.req_stream = env->p.req_stream;
-    h.req_zero = env->p.req_zero;
-    h.bump_day = env->p.bump_day;
+    h.day = DayKey::of(env->p);
     h.gen_mode = env->gen_mode;
     h.gen_loaded = env->gen_loaded ? 1 : 0;
     h.replays = env->replays;
@@ -1642,11 +1616,11 @@ int sng_state_size(const SngEnv *env, int with_return, size_t *bytes) {
 
 int sng_get_state(SngEnv *env, void *buf, size_t bytes, const double *episode_return, void *stream) {
     if (!env || !buf) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
     StateHeader h = state_layout(env, episode_return != nullptr);
     if (bytes < h.total_bytes) return fail(env, SNG_ERR_INVALID_ARGUMENT, "state buffer too small (sng_state_size)");
-    const size_t E = (size_t)env->E, tl = env->timeline();
+    const size_t E = (size_t)env->E;
     char *out = static_cast<char *>(buf) + sizeof(StateHeader);
     auto pull = [&](const void *dev, size_t n) -> hipError_t {
         hipError_t e = hipMemcpyAsync(out, dev, n, hipMemcpyDeviceToHost, st);
@@ -1657,10 +1631,8 @@ int sng_get_state(SngEnv *env, void *buf, size_t bytes, const double *episode_re
     std::vector<uint32_t> np_words, py_words;
     std::vector<int32_t> np_pos, py_pos;
     if (h.has_streams) {
-        int rc = ensure_np_streams(env, st);
-        if (rc) return rc;
-        rc = await_prepare(env, st);
-        if (rc) return rc;
+        SNG_TRY(ensure_np_streams(env, st));
+        SNG_TRY(await_prepare(env, st));
         np_words.resize(E * 2 * kMtN);
         py_words.resize(E * 2 * kMtN);
         np_pos.resize(E);
@@ -1671,17 +1643,7 @@ int sng_get_state(SngEnv *env, void *buf, size_t bytes, const double *episode_re
         HIP_TRY(env, hipMemcpyAsync(py_pos.data(), env->ps.pos, E * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(env, hipMemcpyAsync(&h.day_counter, env->ds.episode, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(env, pull(env->ds.soc, (size_t)env->p.n * E * 8));
-    HIP_TRY(env, pull(env->ds.bess, E * 8));
-    HIP_TRY(env, pull(env->ds.bess0, E * 8));
-    HIP_TRY(env, pull(env->ds.ratio, E * 8));
-    HIP_TRY(env, pull(env->ds.pen0, E * 8));
-    HIP_TRY(env, pull(env->ds.flags, E * 4));
-    if (h.has_word) HIP_TRY(env, pull(env->ds.word, tl * 4));
-    HIP_TRY(env, pull(env->ds.aux, tl * 8));
-    if (h.has_req) HIP_TRY(env, pull(env->ds.req, tl * 8));
-    if (h.has_prof) HIP_TRY(env, pull(env->ds.prof_key, 2 * (size_t)E * 4));
-    if (h.has_return) HIP_TRY(env, pull(episode_return, E * 8));
+    for (const StateSection &x : state_sections(env, h, episode_return)) HIP_TRY(env, pull(x.dev, x.bytes));
     HIP_TRY(env, hipStreamSynchronize(st));
     if (h.has_streams) {
         uint32_t *w = reinterpret_cast<uint32_t *>(out);
@@ -1721,20 +1683,17 @@ int sng_set_state(SngEnv *env, const void *buf, size_t bytes, double *episode_re
     // the sections the header announces must be self-consistent before any of them is read
     auto flag = [](int32_t v) { return v == 0 || v == 1; };
     if (!flag(h.has_word) || !flag(h.has_req) || !flag(h.has_prof) || !flag(h.has_return) || !flag(h.has_streams) ||
-        !flag(h.packed) || h.has_word != 1 - h.packed || state_bytes(env, h) != h.total_bytes)
+        !flag(h.day.packed) || h.has_word != 1 - h.day.packed || state_bytes(env, h) != h.total_bytes)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "corrupt state header (inconsistent sections or size)");
     if (h.total_bytes > bytes) return fail(env, SNG_ERR_INVALID_ARGUMENT, "truncated state");
     if (h.has_return && !episode_return)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "the state holds day returns: pass an episode_return array");
     if ((h.has_prof != 0) != (env->ds.prof_key != nullptr)) return fail(env, SNG_ERR_INVALID_ARGUMENT, "profile mismatch");
     if (h.t < -1 || h.t > env->p.T) return fail(env, SNG_ERR_INVALID_ARGUMENT, "bad timestep in state");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
-    if (h.has_req) {
-        int rc = ensure_req(env);
-        if (rc) return rc;
-    }
-    const size_t E = (size_t)env->E, tl = env->timeline();
+    if (h.has_req) SNG_TRY(ensure_req(env));
+    const size_t E = (size_t)env->E;
     const char *in = static_cast<const char *>(buf) + sizeof(StateHeader);
     auto push = [&](void *dev, size_t n) -> hipError_t {
         hipError_t e = hipMemcpyAsync(dev, in, n, hipMemcpyHostToDevice, st);
@@ -1763,27 +1722,12 @@ int sng_set_state(SngEnv *env, const void *buf, size_t bytes, double *episode_re
                 (k ? py_pos : np_pos)[i] = (int32_t)std::min<uint32_t>(src[kMtN], (uint32_t)kMtN);
             }
         }
-        for (RefStreams *r : {&env->rs, &env->ps}) {
-            if (!r->mt) {
-                HIP_TRY(env, hipMalloc(&r->mt, E * 2 * kMtN * sizeof(uint32_t)));
-                HIP_TRY(env, hipMalloc(&r->pos, E * sizeof(int32_t)));
-            }
-        }
-        int rc = await_prepare(env, st);   // no preparation may still be writing the streams
-        if (rc) return rc;
+        SNG_TRY(alloc_streams(env, env->rs));
+        SNG_TRY(alloc_streams(env, env->ps));
+        SNG_TRY(await_prepare(env, st));   // no preparation may still be writing the streams
     }
     HIP_TRY(env, hipMemcpyAsync(env->ds.episode, &h.day_counter, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(env, push(env->ds.soc, (size_t)env->p.n * E * 8));
-    HIP_TRY(env, push(env->ds.bess, E * 8));
-    HIP_TRY(env, push(env->ds.bess0, E * 8));
-    HIP_TRY(env, push(env->ds.ratio, E * 8));
-    HIP_TRY(env, push(env->ds.pen0, E * 8));
-    HIP_TRY(env, push(env->ds.flags, E * 4));
-    if (h.has_word) HIP_TRY(env, push(env->ds.word, tl * 4));
-    HIP_TRY(env, push(env->ds.aux, tl * 8));
-    if (h.has_req) HIP_TRY(env, push(env->ds.req, tl * 8));
-    if (h.has_prof) HIP_TRY(env, push(env->ds.prof_key, 2 * (size_t)E * 4));
-    if (h.has_return) HIP_TRY(env, push(episode_return, E * 8));
+    for (const StateSection &x : state_sections(env, h, episode_return)) HIP_TRY(env, push(x.dev, x.bytes));
     if (h.has_streams) {
         HIP_TRY(env, hipMemcpy2DAsync(env->rs.mt, 2 * kMtN * sizeof(uint32_t), np_words.data(), kMtN * sizeof(uint32_t),
                                       kMtN * sizeof(uint32_t), E, hipMemcpyHostToDevice, st));
@@ -1798,10 +1742,7 @@ int sng_set_state(SngEnv *env, const void *buf, size_t bytes, double *episode_re
     env->p.env_offset = h.env_offset;
     env->t = h.t;
     env->day_finished = h.day_finished != 0;
-    env->p.packed = h.packed;
-    env->p.req_stream = h.req_stream;
-    env->p.req_zero = h.req_zero;
-    env->p.bump_day = h.bump_day;
+    load_day(env, h.day);
     env->gen_mode = h.gen_mode;
     env->gen_loaded = h.gen_loaded != 0;
     env->replays = h.replays;
@@ -1819,24 +1760,16 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "days must be >= 1 (more than one needs SNG_GRAPH_RESET)");
     if (with_reset && !device_rng_ok(env))
         return fail(env, SNG_ERR_UNSUPPORTED, "device RNG needs time_interval <= 2h");
-    HIP_TRY(env, hipSetDevice(env->device));
-    if (env->p.req_enabled) {
-        int rc = ensure_req(env);
-        if (rc) return rc;
-    }
+    ON_DEVICE_OF(env);
+    if (env->p.req_enabled) SNG_TRY(ensure_req(env));
     hipStream_t cs;
     HIP_TRY(env, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     SngGraph *g = new SngGraph();
     g->env = env;
-    Params p = env->p;
-    if (with_reset) {   // every day a freshly generated device day (sng_reset(SNG_RNG_DEVICE))
-        p.req_stream = p.req_enabled;
-        p.packed = 1;
-        p.req_zero = 0;
-        p.bump_day = 1;
-    }
+    // with a reset: every day a freshly generated device day (sng_reset(SNG_RNG_DEVICE)); else the loaded day
     g->with_reset = with_reset;
-    g->key = day_key(p);
+    g->key = with_reset ? DayKey::device_day(env->p) : DayKey::of(env->p);
+    const Params p = with_day(env->p, g->key);
     g->seed = env->seed;
     g->env_offset = p.env_offset;
     const InfoPtrs ip = info_ptrs(info);
@@ -1873,7 +1806,7 @@ int sng_graph_launch(SngGraph *g, void *stream) {
     SngEnv *env = g->env;
     if (!g->with_reset) {
         // a steps-only graph steps the loaded day from t = 0 with the Params it was captured with
-        if (!(g->key == day_key(env->p)))
+        if (!(g->key == DayKey::of(env->p)))
             return fail(env, SNG_ERR_STATE,
                         "graph captured for a day of another encoding (RNG mode, requested-SoC stream or replay): "
                         "recapture it after this reset");
@@ -1883,27 +1816,21 @@ int sng_graph_launch(SngGraph *g, void *stream) {
     // still draw the old streams
     if (g->seed != env->seed || g->env_offset != env->p.env_offset)
         return fail(env, SNG_ERR_STATE, "seed or env offset changed since the graph was captured: recapture it");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     // the graph's first reset must not redraw a device day that was reset but never stepped
-    if (g->with_reset && env->p.packed && env->p.bump_day && env->t == 0)
-        HIP_TRY(env, launch_bump_day(env->ds, as_stream(stream)));
+    if (g->with_reset) HIP_TRY(env, count_unstepped_device_day(env, as_stream(stream)));
     HIP_TRY(env, hipGraphLaunch(g->exec, as_stream(stream)));
     if (g->with_reset) {
-        env->p.req_stream = env->p.req_enabled;
-        env->p.packed = 1;
-        env->p.req_zero = 0;
-        env->p.bump_day = 1;
-        env->gen_mode = SNG_RNG_DEVICE;
-        env->gen_loaded = true;
+        load_day(env, g->key);
+        generated_day_loaded(env, SNG_RNG_DEVICE);
     }
-    env->t = env->p.T;
-    env->day_finished = true;
+    days_ran(env);
     return SNG_OK;
 }
 
 void sng_graph_destroy(SngGraph *g) {
     if (!g) return;
-    (void)hipSetDevice(g->env->device);
+    DeviceScope scope(g->env->device);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     if (g->graph) (void)hipGraphDestroy(g->graph);
     delete g;
@@ -1914,24 +1841,17 @@ int sng_time_step_kernels(SngEnv *env, const float *actions, float *obs, double 
     if (!env || !actions || !obs || !reward || !done || days < 1)
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
     if (!device_rng_ok(env)) return fail(env, SNG_ERR_UNSUPPORTED, "device RNG needs time_interval <= 2h");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     hipStream_t st = as_stream(stream);
-    Params p = env->p;
-    p.req_stream = p.req_enabled;
-    p.packed = 1;
-    p.req_zero = 0;
-    p.bump_day = 1;
-    if (p.req_stream) {
-        int rc = ensure_req(env);
-        if (rc) return rc;
-    }
+    const DayKey key = DayKey::device_day(env->p);
+    const Params p = with_day(env->p, key);
+    if (p.req_stream) SNG_TRY(ensure_req(env));
     const InfoPtrs ip = info_ptrs(info);
     const int64_t E = env->E;
     const int T = p.T, A = p.act_dim;
     const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
     std::vector<hipEvent_t> ev(ms ? 2 * (size_t)T * days : 0, nullptr), rev(reset_ms ? 2 * (size_t)days : 0, nullptr);
-    hipError_t e = hipSuccess;
-    if (env->p.packed && env->p.bump_day && env->t == 0) e = launch_bump_day(env->ds, st);   // as in sng_reset
+    hipError_t e = count_unstepped_device_day(env, st);   // as in sng_reset
     for (auto &x : ev)
         if (e == hipSuccess) e = hipEventCreate(&x);
     for (auto &x : rev)
@@ -1953,14 +1873,9 @@ int sng_time_step_kernels(SngEnv *env, const float *actions, float *obs, double 
     for (auto x : rev)
         if (x) (void)hipEventDestroy(x);
     if (e != hipSuccess) return hip_fail(env, e, "timed day");
-    env->p.req_stream = p.req_stream;
-    env->p.packed = 1;
-    env->p.req_zero = 0;
-    env->p.bump_day = 1;
-    env->gen_mode = SNG_RNG_DEVICE;
-    env->gen_loaded = true;
-    env->t = T;
-    env->day_finished = true;
+    load_day(env, key);
+    generated_day_loaded(env, SNG_RNG_DEVICE);
+    days_ran(env);
     return SNG_OK;
 }
 
@@ -1968,7 +1883,8 @@ int sng_bandwidth_probe(int device, int64_t read_bytes, int64_t write_bytes, int
                         float *back_to_back_us, void *stream) {
     if (read_bytes < 0 || write_bytes < 0 || read_bytes + write_bytes < 16 || reps < 1)
         return fail(nullptr, SNG_ERR_INVALID_ARGUMENT, "sng_bandwidth_probe: bad sizes");
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, SNG_ERR_HIP, "sng_bandwidth_probe: hipSetDevice");
+    DeviceScope scope(device);
+    if (scope.err != hipSuccess) return fail(nullptr, SNG_ERR_HIP, "sng_bandwidth_probe: hipSetDevice");
     hipStream_t st = as_stream(stream);
     const int64_t nr = read_bytes / 16, nw = write_bytes / 16;
     void *in = nullptr, *out = nullptr;
@@ -2037,7 +1953,7 @@ int32_t sng_host_threads(void) { return host_threads(); }
 int sng_get_day_counter(SngEnv *env, uint64_t *out, void *stream) {
     if (!env) return SNG_ERR_INVALID_ARGUMENT;
     if (!out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "sng_get_day_counter: null output");
-    HIP_TRY(env, hipSetDevice(env->device));
+    ON_DEVICE_OF(env);
     HIP_TRY(env, hipMemcpyAsync(out, env->ds.episode, sizeof(uint64_t), hipMemcpyDeviceToHost, as_stream(stream)));
     HIP_TRY(env, hipStreamSynchronize(as_stream(stream)));
     return SNG_OK;

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "sng.h"
+#include "sng_device_scope.h"
 
 static_assert(SNG_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 
@@ -97,8 +98,9 @@ int sng_comm_create(int device, int nranks, int rank, const uint8_t *id, SngComm
     if (nranks < 1 || rank < 0 || rank >= nranks) return comm_fail(nullptr, SNG_ERR_INVALID_ARGUMENT, "bad rank");
     const Rccl &r = rccl();
     if (!r.error.empty()) return comm_fail(nullptr, SNG_ERR_UNSUPPORTED, r.error);
-    hipError_t he = hipSetDevice(device);
-    if (he != hipSuccess) return comm_fail(nullptr, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+    sng::DeviceScope dev(device);
+    if (dev.err != hipSuccess)
+        return comm_fail(nullptr, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev.err));
     ncclUniqueId uid;
     std::memcpy(uid.internal, id, SNG_COMM_ID_BYTES);
     SngComm *c = new SngComm();
@@ -117,8 +119,9 @@ int sng_comm_create(int device, int nranks, int rank, const uint8_t *id, SngComm
 int sng_allgather_returns(SngComm *comm, const double *local, double *global, int64_t count, void *stream) {
     if (!comm) return comm_fail(nullptr, SNG_ERR_INVALID_ARGUMENT, "null communicator");
     if (!local || !global || count < 1) return comm_fail(comm, SNG_ERR_INVALID_ARGUMENT, "bad buffers");
-    hipError_t he = hipSetDevice(comm->device);
-    if (he != hipSuccess) return comm_fail(comm, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+    sng::DeviceScope dev(comm->device);
+    if (dev.err != hipSuccess)
+        return comm_fail(comm, SNG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev.err));
     ncclResult_t e = rccl().all_gather(local, global, (size_t)count, ncclFloat64, comm->comm, (hipStream_t)stream);
     if (e != ncclSuccess) return comm_fail(comm, SNG_ERR_HIP, nccl_msg("ncclAllGather", e));
     return SNG_OK;
@@ -126,6 +129,7 @@ int sng_allgather_returns(SngComm *comm, const double *local, double *global, in
 
 void sng_comm_destroy(SngComm *comm) {
     if (!comm) return;
+    sng::DeviceScope dev(comm->device);
     if (comm->comm) (void)rccl().destroy(comm->comm);
     delete comm;
 }

@@ -19,12 +19,13 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <type_traits>
 
 #include "sng.h"
+#include "sng_launch.h"
 #include "sng_layout.h"
+#include "sng_step_plan.h"
 
 namespace sng {
 
@@ -2135,159 +2136,120 @@ __global__ __launch_bounds__(256) void probe_copy_kernel(const float4 *__restric
     if (i < nw) __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(out) + i);
 }
 
+// ---------------------------------------------------------------------------------
+// launch wrappers (called from sng_api.cpp, declared in sng_launch.h)
+// ---------------------------------------------------------------------------------
+// One launch, with optional start/stop events (both or neither): hipExtLaunchKernel stamps them with the
+// dispatch's own begin/end timestamps, i.e. the kernel's device time.
+template <class Kernel, class... Args>
+static hipError_t launch_kernel(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                                hipEvent_t ev_start, hipEvent_t ev_stop, Args... args) {
+    if (ev_start && ev_stop)
+        hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, stream, ev_start, ev_stop, 0u, args...);
+    else
+        hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
 hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,
                              hipEvent_t b) {
     const int64_t n = nr > nw ? nr : nw;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (a && b)
-        hipExtLaunchKernelGGL(probe_copy_kernel, grid, block, 0, stream, a, b, 0u, (const float4 *)in, (float4 *)out,
-                              nr, nw);
-    else
-        hipLaunchKernelGGL(probe_copy_kernel, grid, block, 0, stream, (const float4 *)in, (float4 *)out, nr, nw);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
-// launch wrappers (called from sng_api.cpp)
-// ---------------------------------------------------------------------------------
-// Optional start/stop events: hipExtLaunchKernel stamps them with the dispatch's own
-// begin/end timestamps, i.e. the kernel's device time.
-struct LaunchEvents {
-    hipEvent_t start = nullptr, stop = nullptr;
-};
-
-// Stations of 10 chargers without V2X (the headline configuration) step through the wide kernel with two
-// lanes per env: A/B at 65,536 x 10 x 24 (round 3's tools/ab_headline.sh, in commits before 8be1f55; three runs each) 6.47-6.51 us per step
-// in the day graph vs 6.67-6.71 for the lean kernel, day 0.1749-0.1761 vs 0.1796-0.1803 ms; one lane per
-// env 6.75-6.79, four 8.15-8.23.  With V2X a discharging action is routine, and the lean kernel's LDS rows
-// keep numpy's order cheaper than the wide kernel's rolled re-read.
-// The lean step kernel's configurations: a compile-time station of N <= 16, one lane per env, no
-// diagnostics, NumPy-2 promotion with a power-of-two dt, no stochastic profiles.
-static bool lean_step(const Params &p, bool diag) {
-    const bool nc = p.n == 1 || p.n == 2 || p.n == 4 || p.n == 8 || (p.n == 10 && p.v2x) ||
-                    p.n == 16;
-    return nc && !diag && !p.legacy && p.dt_pow2 && !p.noise && !(p.lanes == 2 || p.lanes == 4);
-}
-
-template <int NC>
-static void launch_lean(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
-                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
-                        hipStream_t stream, const LaunchEvents *ev) {
-    StepConst k;
-    for (int i = 0; i < CST_COUNT; ++i) k.v[i] = step_constant(&tab, t, i);
-    const bool req = p.req_stream && !p.req_zero;
-    auto kern = p.packed ? (req ? step_lean_kernel<NC, true, true> : step_lean_kernel<NC, true, false>)
-                         : (req ? step_lean_kernel<NC, false, true> : step_lean_kernel<NC, false, false>);
-    const dim3 grid((unsigned)((E + kLeanBlock - 1) / kLeanBlock)), block(kLeanBlock);
-    const uint32_t lds = (uint32_t)LeanLds<NC>::BYTES;
-    if (ev)
-        hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ev->start, ev->stop, 0u, act, obs, reward, done, E, t,
-                              vec_io, k, p, s, info);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, act, obs, reward, done, E, t, vec_io, k, p, s, info);
-}
-
-// The wide lean step kernel's configurations: N = 50 (BASELINE config 5's station), one lane per env, no
-// diagnostics, NumPy-2 promotion with a power-of-two dt; stochastic profiles allowed.
-static bool wide_step(const Params &p, bool diag) {
-    return (p.n == 50 || (p.n == 10 && !p.noise && !p.v2x)) && !diag && !p.legacy && p.dt_pow2 &&
-           !(p.lanes == 2 || p.lanes == 4);
-}
-
-// Lanes per env of the wide lean step kernel: two (2,048 wavefronts at 65,536 envs, two per SIMD).
-// A/B at config 5 (round 3's tools/wide_ab.sh, in commits before 8be1f55; two runs each): 1 lane 25.85-25.91 us per step in the day graph,
-// 2 lanes 22.54-22.62, 4 lanes 30.36-30.49 (128 VGPRs: 40 spilled to scratch).
-__host__ __device__ constexpr int wide_lanes(int) { return 2; }
-
-template <int NC>
-static void launch_wide(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
-                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
-                        hipStream_t stream, const LaunchEvents *ev) {
-    constexpr int L = wide_lanes(NC);
-    StepConst k;
-    for (int i = 0; i < CST_COUNT; ++i) k.v[i] = step_constant(&tab, t, i);
-    const bool req = p.req_stream && !p.req_zero;
-    const int v = (p.packed ? 4 : 0) | (req ? 2 : 0) | (p.noise ? 1 : 0);
-    void (*kerns[8])(const float *, float *, double *, uint8_t *, int64_t, int, int, StepConst, Params, DeviceState,
-                     InfoPtrs) = {
-        step_wide_kernel<NC, L, false, false, false>, step_wide_kernel<NC, L, false, false, true>,
-        step_wide_kernel<NC, L, false, true, false>,  step_wide_kernel<NC, L, false, true, true>,
-        step_wide_kernel<NC, L, true, false, false>,  step_wide_kernel<NC, L, true, false, true>,
-        step_wide_kernel<NC, L, true, true, false>,   step_wide_kernel<NC, L, true, true, true>};
-    auto kern = kerns[v];
-    using Lay = WideLds<NC, L>;
-    constexpr int ENVS = Lay::WENVS;   // envs per wavefront
-    const dim3 grid((unsigned)((E + ENVS - 1) / ENVS)), block(kWave);
-    const uint32_t lds = (uint32_t)((size_t)(Lay::ACT + Lay::OBS) * 4);
-    if (ev)
-        hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ev->start, ev->stop, 0u, act, obs, reward, done, E, t,
-                              vec_io, k, p, s, info);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, act, obs, reward, done, E, t, vec_io, k, p, s, info);
-}
-
-static void launch_lean_n(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
-                          const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
-                          hipStream_t stream, const LaunchEvents *ev) {
-    switch (p.n) {
-        case 1: launch_lean<1>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 2: launch_lean<2>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 4: launch_lean<4>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 8: launch_lean<8>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 10: launch_lean<10>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        default: launch_lean<16>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-    }
-}
-
-template <int NC, int L, bool DIAG>
-static void launch_step_t(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                          double *reward, uint8_t *done, int64_t E, int t, int vec_io, hipStream_t stream,
-                          const LaunchEvents *ev) {
-    using Lay = StepLds<NC, L>;
-    const dim3 grid((unsigned)((E + Lay::ENVS - 1) / Lay::ENVS)), block(Lay::BLOCK);
-    const uint32_t lds = (uint32_t)Lay::bytes(p.act_dim, p.obs_dim);
-    const bool fast = !p.legacy && p.dt_pow2;
-    auto kern = p.packed ? (fast ? step_kernel<NC, L, DIAG, true, true> : step_kernel<NC, L, DIAG, false, true>)
-                         : (fast ? step_kernel<NC, L, DIAG, true, false> : step_kernel<NC, L, DIAG, false, false>);
-    if (ev)
-        hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ev->start, ev->stop, 0u, p, s, info, act, obs, reward,
-                              done, E, t, vec_io);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, p, s, info, act, obs, reward, done, E, t, vec_io);
-}
-
-template <int NC, bool DIAG>
-static void launch_step_l(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                          double *reward, uint8_t *done, int64_t E, int t, int vec_io, hipStream_t stream,
-                          const LaunchEvents *ev) {
-    switch (p.lanes) {
-        case 4: launch_step_t<NC, 4, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 2: launch_step_t<NC, 2, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        default: launch_step_t<NC, 1, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-    }
-}
-
-template <bool DIAG>
-static void launch_step_n(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                          double *reward, uint8_t *done, int64_t E, int t, int vec_io, hipStream_t stream,
-                          const LaunchEvents *ev) {
-    switch (p.n) {
-        case 1: launch_step_t<1, 1, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 2: launch_step_l<2, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 4: launch_step_l<4, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 8: launch_step_l<8, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 10: launch_step_l<10, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 16: launch_step_l<16, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        case 50: launch_step_l<50, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-        default: launch_step_t<0, 1, DIAG>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev); break;
-    }
+    return launch_kernel(probe_copy_kernel, grid, block, 0, stream, a, b, (const float4 *)in, (float4 *)out, nr, nw);
 }
 
 SNG_DIAG_SET_STAMPS   // diagnostic builds: sng_debug_set_stamps
 
-int step_lanes_supported(int n, int lanes) {
-    const bool multi = (n == 2 || n == 4 || n == 8 || n == 10 || n == 16 || n == 50);
-    return (lanes == 1 || (multi && (lanes == 2 || lanes == 4))) ? 1 : 0;
+int step_lanes_supported(int n, int lanes) { return station_lanes_supported(n, lanes) ? 1 : 0; }
+
+// A plan's kernel and launch geometry.  The lean and the wide kernel share one signature (this step's table
+// constants by value, StepConst); the general kernel reads them through the tables pointer.
+typedef void (*ConstStepKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, StepConst, Params,
+                                DeviceState, InfoPtrs);
+typedef void (*GeneralStepKernel)(Params, DeviceState, InfoPtrs, const float *, float *, double *, uint8_t *, int64_t,
+                                  int, int);
+struct StepLaunch {
+    ConstStepKernel by_const = nullptr;   // STEP_LEAN, STEP_WIDE
+    GeneralStepKernel general = nullptr;   // STEP_GENERAL
+    dim3 grid, block;
+    size_t lds = 0;
+};
+
+static dim3 blocks_for(int64_t E, int envs_per_block) { return dim3((unsigned)((E + envs_per_block - 1) / envs_per_block)); }
+
+template <int NC>
+static StepLaunch lean_launch(const StepPlan &pl, int64_t E) {
+    static constexpr ConstStepKernel k[2][2] = {{step_lean_kernel<NC, false, false>, step_lean_kernel<NC, false, true>},
+                                                {step_lean_kernel<NC, true, false>, step_lean_kernel<NC, true, true>}};
+    return {k[pl.pk][pl.req], nullptr, blocks_for(E, kLeanBlock), dim3(kLeanBlock), LeanLds<NC>::BYTES};
+}
+
+template <int NC>
+static StepLaunch wide_launch(const StepPlan &pl, int64_t E) {
+    constexpr int L = kWideLanes;
+    static constexpr ConstStepKernel k[2][2][2] = {
+        {{step_wide_kernel<NC, L, false, false, false>, step_wide_kernel<NC, L, false, false, true>},
+         {step_wide_kernel<NC, L, false, true, false>, step_wide_kernel<NC, L, false, true, true>}},
+        {{step_wide_kernel<NC, L, true, false, false>, step_wide_kernel<NC, L, true, false, true>},
+         {step_wide_kernel<NC, L, true, true, false>, step_wide_kernel<NC, L, true, true, true>}}};
+    using Lay = WideLds<NC, L>;   // one wavefront of WENVS envs per workgroup
+    return {k[pl.pk][pl.req][pl.noise], nullptr, blocks_for(E, Lay::WENVS), dim3(kWave), Lay::BYTES};
+}
+
+template <int NC, int L>
+static StepLaunch general_launch(const StepPlan &pl, const Params &p, int64_t E) {
+    static constexpr GeneralStepKernel k[2][2][2] = {
+        {{step_kernel<NC, L, false, false, false>, step_kernel<NC, L, false, false, true>},
+         {step_kernel<NC, L, false, true, false>, step_kernel<NC, L, false, true, true>}},
+        {{step_kernel<NC, L, true, false, false>, step_kernel<NC, L, true, false, true>},
+         {step_kernel<NC, L, true, true, false>, step_kernel<NC, L, true, true, true>}}};
+    using Lay = StepLds<NC, L>;
+    return {nullptr, k[pl.diag][pl.fast][pl.pk], blocks_for(E, Lay::ENVS), dim3(Lay::BLOCK),
+            Lay::bytes(p.act_dim, p.obs_dim)};
+}
+
+template <int NC>
+static StepLaunch general_launch_lanes(const StepPlan &pl, const Params &p, int64_t E) {
+    return pl.lanes == 4   ? general_launch<NC, 4>(pl, p, E)
+           : pl.lanes == 2 ? general_launch<NC, 2>(pl, p, E)
+                           : general_launch<NC, 1>(pl, p, E);
+}
+
+// The map from a plan to its kernel: one case per compiled station size of kStationSizes (sng_step_plan.h).  A
+// plan without a case here has no kernel (launch_step fails; tests/test_step_plan_cpu.py holds every name a
+// plan can give against the code object's symbols).
+static StepLaunch step_launch(const StepPlan &pl, const Params &p, int64_t E) {
+    switch (pl.family) {
+        case STEP_LEAN:
+            switch (pl.nc) {
+                case 1: return lean_launch<1>(pl, E);
+                case 2: return lean_launch<2>(pl, E);
+                case 4: return lean_launch<4>(pl, E);
+                case 8: return lean_launch<8>(pl, E);
+                case 10: return lean_launch<10>(pl, E);
+                case 16: return lean_launch<16>(pl, E);
+            }
+            break;
+        case STEP_WIDE:
+            switch (pl.nc) {
+                case 10: return wide_launch<10>(pl, E);
+                case 50: return wide_launch<50>(pl, E);
+            }
+            break;
+        case STEP_GENERAL:
+            switch (pl.nc) {
+                case 0: return general_launch<0, 1>(pl, p, E);
+                case 1: return general_launch<1, 1>(pl, p, E);
+                case 2: return general_launch_lanes<2>(pl, p, E);
+                case 4: return general_launch_lanes<4>(pl, p, E);
+                case 8: return general_launch_lanes<8>(pl, p, E);
+                case 10: return general_launch_lanes<10>(pl, p, E);
+                case 16: return general_launch_lanes<16>(pl, p, E);
+                case 50: return general_launch_lanes<50>(pl, p, E);
+            }
+            break;
+    }
+    return {};
 }
 
 // The step kernel writes the diagnostics (DIAG) when any SngInfo array other than the flags and the
@@ -2301,71 +2263,34 @@ static bool info_diag(const InfoPtrs &info) {
 hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
                        hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    LaunchEvents evs{ev_start, ev_stop};
-    const LaunchEvents *ev = (ev_start && ev_stop) ? &evs : nullptr;
-    if (lean_step(p, info_diag(info))) {
-        launch_lean_n(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev);
-        return hipGetLastError();
-    }
-    if (wide_step(p, info_diag(info))) {
-        if (p.n == 10)
-            launch_wide<10>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev);
-        else
-            launch_wide<50>(p, s, info, tab, act, obs, reward, done, E, t, vec_io, stream, ev);
-        return hipGetLastError();
-    }
-    if (info_diag(info))
-        launch_step_n<true>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev);
-    else
-        launch_step_n<false>(p, s, info, act, obs, reward, done, E, t, vec_io, stream, ev);
-    return hipGetLastError();
+    const StepLaunch l = step_launch(step_plan(p, info_diag(info)), p, E);
+    if (l.general)
+        return launch_kernel(l.general, l.grid, l.block, l.lds, stream, ev_start, ev_stop, p, s, info, act, obs, reward,
+                             done, E, t, vec_io);
+    if (!l.by_const) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
+    StepConst k;
+    for (int i = 0; i < CST_COUNT; ++i) k.v[i] = step_constant(&tab, t, i);
+    return launch_kernel(l.by_const, l.grid, l.block, l.lds, stream, ev_start, ev_stop, act, obs, reward, done, E, t,
+                         vec_io, k, p, s, info);
 }
 
-// The name rocprofv3 reports for the step kernel launch_step would dispatch next (the template
-// arguments launch_step_n / launch_step_l / launch_step_t select).
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len) {
-    if (lean_step(p, info_diag(info)))
-        return snprintf(buf, (size_t)len, "void sng::step_lean_kernel<%d, %s, %s>", p.n, p.packed ? "true" : "false",
-                        (p.req_stream && !p.req_zero) ? "true" : "false");
-    if (wide_step(p, info_diag(info)))
-        return snprintf(buf, (size_t)len, "void sng::step_wide_kernel<%d, %d, %s, %s, %s>", p.n, wide_lanes(p.n),
-                        p.packed ? "true" : "false", (p.req_stream && !p.req_zero) ? "true" : "false",
-                        p.noise ? "true" : "false");
-    int nc = 0, lanes = 1;
-    switch (p.n) {
-        case 2: case 4: case 8: case 10: case 16: case 50:
-            nc = p.n;
-            lanes = (p.lanes == 2 || p.lanes == 4) ? p.lanes : 1;
-            break;
-        case 1: nc = 1; break;
-        default: nc = 0; break;
-    }
-    const bool fast = !p.legacy && p.dt_pow2;
-    return snprintf(buf, (size_t)len, "void sng::step_kernel<%d, %d, %s, %s, %s>", nc, lanes,
-                    info_diag(info) ? "true" : "false", fast ? "true" : "false", p.packed ? "true" : "false");
+    return step_plan_name(step_plan(p, info_diag(info)), buf, len);
 }
 
 hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
-                           int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
-                           int py = 0) {
+                           int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps, int py) {
     const RefStreams no_streams{nullptr, nullptr};
     const RefStreams &pss = (py && ps) ? *ps : no_streams;
     if (!ps) py = 0;
-    if ((size_t)round4(256 * p.obs_dim) * 4 <= 64 * 1024) {
-        const dim3 grid((unsigned)((E + 255) / 256)), block(256);
-        auto kern = p.packed ? observe0_kernel<256, true> : observe0_kernel<256, false>;
-        hipLaunchKernelGGL(kern, grid, block, (size_t)round4(256 * p.obs_dim) * 4, stream, p, s, obs, ep_return, E,
-                           vec_io, mode, replay, pss, py);
-    } else {
-        const dim3 grid((unsigned)((E + kWave - 1) / kWave)), block(kWave);
-        auto kern = p.packed ? observe0_kernel<kWave, true> : observe0_kernel<kWave, false>;
-        hipLaunchKernelGGL(kern, grid, block, (size_t)round4(kWave * p.obs_dim) * 4, stream, p, s, obs, ep_return, E,
-                           vec_io, mode, replay, pss, py);
-    }
-    return hipGetLastError();
+    // 256 envs per workgroup while their [256][obs_dim] LDS tile fits 64 KB, else one wavefront's
+    const bool big = (size_t)round4(256 * p.obs_dim) * 4 <= 64 * 1024;
+    const int envs = big ? 256 : kWave;
+    auto kern = big ? (p.packed ? observe0_kernel<256, true> : observe0_kernel<256, false>)
+                    : (p.packed ? observe0_kernel<kWave, true> : observe0_kernel<kWave, false>);
+    return launch_kernel(kern, blocks_for(E, envs), dim3(envs), (size_t)round4(envs * p.obs_dim) * 4, stream, nullptr,
+                         nullptr, p, s, obs, ep_return, E, vec_io, mode, replay, pss, py);
 }
-
-hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
 
 // A whole device-RNG reset.  The t = 0 observation runs as extra blocks of the generator's grid
 // while its [256][obs_dim] LDS tile stays small next to the vehicle lists (N <= 16: at most 42 KB,
@@ -2383,14 +2308,12 @@ hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed,
     auto kern = p.T == 24 ? (req ? generate_kernel<24, true> : generate_kernel<24, false>)
                 : (p.T == 96 && !req) ? generate_kernel<96, false>   // config 5's 15-minute day
                 : (req ? generate_kernel<0, true> : generate_kernel<0, false>);
-    if (fused && ev_start && ev_stop) {   // the one-launch reset, timed by its own dispatch timestamps
-        hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ev_start, ev_stop, 0u, p, s, seed, E, i4, i10, i1, obs,
-                              ep_return, vec_io);
-        return hipGetLastError();
-    }
+    if (fused && ev_start && ev_stop)   // the one-launch reset, timed by its own dispatch timestamps
+        return launch_kernel(kern, grid, block, lds, stream, ev_start, ev_stop, p, s, seed, E, i4, i10, i1, obs,
+                             ep_return, vec_io);
     if (ev_start) (void)hipEventRecord(ev_start, stream);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, p, s, seed, E, i4, i10, i1, obs, ep_return, vec_io);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, p, s, seed, E, i4, i10, i1, obs,
+                                 ep_return, vec_io);
     if (!fused) {
         if (e == hipSuccess) e = launch_profiles(p, s, E, stream);
         // the PV ratio and pen0 of the day, from the streams, as the fused t = 0 blocks do
@@ -2977,13 +2900,13 @@ hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipS
     return hipGetLastError();
 }
 
-// One reference-RNG day of every env into the word / aux (/ req) planes; ratio, pen0 and the t = 0
-// observation are the caller's (the Python stream stays on the host).
 hipError_t launch_mt_prepare(const RefStreams &rs, int64_t E, hipStream_t stream) {
     hipLaunchKernelGGL(mt_prepare_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0, stream, rs, E);
     return hipGetLastError();
 }
 
+// One reference-RNG day of every env into the word / aux (/ req) planes; ratio, pen0 and the t = 0
+// observation are the caller's (launch_observe0, which draws the Python streams).
 // prepare = false: the streams' blocks were prepared for this day already (sng_api.cpp prepares the next
 // day's on a side stream while a day is stepped)
 hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStreams &rs, int64_t E, int i4, int i10,
@@ -3002,7 +2925,6 @@ hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStream
     }
     return hipGetLastError();
 }
-
 
 __global__ void bump_day_kernel(DeviceState s) { *s.episode += 1; }
 

@@ -1,0 +1,32 @@
+// sng_launch.h -- what sng_api.cpp calls in sng_kernels.hip.  Both include it, so a changed signature is a
+// compile error in one of them; default arguments live here only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "sng_layout.h"
+
+namespace sng {
+
+// ev_start / ev_stop (both or neither): stamped with the dispatch's own begin / end, the kernel's device time
+hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
+                       const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
+                       hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
+                           int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
+                           int py = 0);
+hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4, int i10, int i1,
+                           float *obs, double *ep_return, int vec_io, hipStream_t stream,
+                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
+hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream);
+hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,
+                             hipEvent_t b);
+hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipStream_t stream);
+hipError_t launch_mt_prepare(const RefStreams &rs, int64_t E, hipStream_t stream);
+hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStreams &rs, int64_t E, int i4, int i10,
+                          int i1, bool prepare, hipStream_t stream);
+int step_lanes_supported(int n, int lanes);
+// The name rocprofv3 reports for the step kernel launch_step would dispatch next.
+int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);
+
+}  // namespace sng

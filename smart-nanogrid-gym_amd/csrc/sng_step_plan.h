@@ -1,0 +1,95 @@
+// sng_step_plan.h -- which step kernel a handle's Params select, decided once.
+//
+// launch_step (sng_kernels.hip) dispatches the kernel a plan names and step_kernel_name formats the same plan
+// as the name rocprofv3 reports, so the two cannot disagree.  Host only, no HIP types: it compiles with plain
+// g++ (tests/native/step_plan_check.cpp lists the name of every configuration on the CPU).
+#pragma once
+#include <stdio.h>
+
+#include "sng_layout.h"
+
+namespace sng {
+
+// The station sizes the step kernels are compiled for: n, then whether step_lean_kernel<n, ...>,
+// step_wide_kernel<n, kWideLanes, ...> and step_kernel<n, L, ...> with L = 2 and 4 lanes per env exist.  Any
+// other charger count runs the general kernel with a runtime N (NC = 0), one lane per env.
+struct StationSize {
+    int n;
+    bool lean, wide, lanes;
+};
+constexpr StationSize kStationSizes[] = {
+    {1, true, false, false}, {2, true, false, true},  {4, true, false, true},  {8, true, false, true},
+    {10, true, true, true},  {16, true, false, true}, {50, false, true, true},
+};
+inline const StationSize *station_size(int n) {
+    for (const StationSize &s : kStationSizes)
+        if (s.n == n) return &s;
+    return nullptr;
+}
+
+// SngConfig.step_lanes_per_env (bench.py --lanes): one lane everywhere, two or four at the compiled sizes > 1.
+inline bool station_lanes_supported(int n, int lanes) {
+    const StationSize *s = station_size(n);
+    return lanes == 1 || ((lanes == 2 || lanes == 4) && s && s->lanes);
+}
+
+// Lanes per env of the wide step kernel: two (2,048 wavefronts at 65,536 envs, two per SIMD).
+// A/B at config 5 (round 3's tools/wide_ab.sh, in commits before 8be1f55; two runs each): 1 lane 25.85-25.91 us per step in the day graph,
+// 2 lanes 22.54-22.62, 4 lanes 30.36-30.49 (128 VGPRs: 40 spilled to scratch).
+constexpr int kWideLanes = 2;
+
+enum StepFamily : int {
+    STEP_LEAN,      // step_lean_kernel<NC, PK, REQ>
+    STEP_WIDE,      // step_wide_kernel<NC, L, PK, REQ, NOISE>
+    STEP_GENERAL,   // step_kernel<NC, L, DIAG, FAST, PK>
+};
+
+struct StepPlan {
+    StepFamily family;
+    int nc;      // compile-time charger count, 0 for a runtime N
+    int lanes;   // lanes per env
+    // the template flags (each family takes its own subset, above): the day is packed records (device-RNG days);
+    // the requested-SoC stream is read; stochastic PV / price profiles; the SngInfo diagnostics are written;
+    // NumPy-2 promotion with a power-of-two dt
+    bool pk, req, noise, diag, fast;
+};
+
+// The lean and the wide kernel both take a compiled station, one lane per env as configured (they choose
+// their own lanes), no diagnostics, and NumPy-2 promotion with a power-of-two dt.  Between them:
+//   - the lean kernel (N <= 16, no stochastic profiles) is the default;
+//   - stations of 10 chargers without V2X (the headline configuration) step through the wide kernel with two
+//     lanes per env: A/B at 65,536 x 10 x 24 (round 3's tools/ab_headline.sh, in commits before 8be1f55; three runs each) 6.47-6.51 us per step
+//     in the day graph vs 6.67-6.71 for the lean kernel, day 0.1749-0.1761 vs 0.1796-0.1803 ms; one lane per
+//     env 6.75-6.79, four 8.15-8.23.  With V2X a discharging action is routine, and the lean kernel's LDS rows
+//     keep numpy's order cheaper than the wide kernel's rolled re-read;
+//   - N = 50 (BASELINE config 5's station) is the wide kernel's, stochastic profiles included.
+// Everything else is the general kernel's: diagnostics, legacy promotion, another dt, a configured lane
+// count of 2 or 4, stochastic profiles at N <= 16, a charger count that is not compiled in.
+inline StepPlan step_plan(const Params &p, bool diag) {
+    const StationSize *sz = station_size(p.n);
+    const bool multi = p.lanes == 2 || p.lanes == 4, fast = !p.legacy && p.dt_pow2, noise = p.noise != 0;
+    const bool special = sz && fast && !diag && !multi;
+    StepPlan pl{STEP_GENERAL, sz ? p.n : 0, (multi && sz && sz->lanes) ? p.lanes : 1,
+                p.packed != 0, p.req_stream && !p.req_zero, noise, diag, fast};
+    if (special && sz->lean && !noise && (p.n != 10 || p.v2x)) {
+        pl.family = STEP_LEAN;
+    } else if (special && sz->wide && (p.n != 10 || (!noise && !p.v2x))) {
+        pl.family = STEP_WIDE;
+        pl.lanes = kWideLanes;
+    }
+    return pl;
+}
+
+// The name rocprofv3 reports for a plan's kernel (bench.py looks its kernel-stats and PMC records up by it).
+inline int step_plan_name(const StepPlan &pl, char *buf, int len) {
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    if (pl.family == STEP_LEAN)
+        return snprintf(buf, (size_t)len, "void sng::step_lean_kernel<%d, %s, %s>", pl.nc, b(pl.pk), b(pl.req));
+    if (pl.family == STEP_WIDE)
+        return snprintf(buf, (size_t)len, "void sng::step_wide_kernel<%d, %d, %s, %s, %s>", pl.nc, pl.lanes,
+                        b(pl.pk), b(pl.req), b(pl.noise));
+    return snprintf(buf, (size_t)len, "void sng::step_kernel<%d, %d, %s, %s, %s>", pl.nc, pl.lanes, b(pl.diag),
+                    b(pl.fast), b(pl.pk));
+}
+
+}  // namespace sng

@@ -1,0 +1,10 @@
+# The library's sources and its build id, shared by csrc/Makefile and tools/diag/Makefile (tools/diag/variant.sh
+# copies csrc/ whole, so this fragment travels with a variant's sources).
+SNG_SRCS := sng_kernels.hip sng_api.cpp sng_comm.cpp
+SNG_HDRS := sng_layout.h sng_mt.h sng_diag_hooks.h sng_launch.h sng_step_plan.h sng_device_scope.h
+# $(call sng_build_id,<csrc directory>,<compile flags>): the first 12 hex digits of the SHA-256 of every source
+# of the library, the compile flags and the compiler's version line (the same sources built with
+# other flags or another ROCm are another binary).  The committed measurements under profiles/ are keyed by
+# it (bench.py looks them up by the loaded library's id).
+sng_build_id = $(shell (cd $(1) && cat $(SNG_SRCS) $(SNG_HDRS) $(ROOT)/include/sng.h; echo '$(2)'; \
+                        $(HIPCC) --version 2>/dev/null | head -1) | sha256sum | cut -c1-12)

@@ -416,3 +416,51 @@ def test_load_state_rebuilds_the_flag_summary():
     assert not any("v2x_breakpoint" in d for d in infos)
     a.close()
     b.close()
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
+def test_entry_points_keep_the_callers_device():
+    """Every entry point selects the handle's device for the length of the call only (DESIGN.md section 0 item
+    6): with device 0 current, a handle on device 1 is driven through resets in both RNG modes, steps, the
+    error check, a checkpoint round trip, a scenario export, a one-day graph and both closes, and device 0 is
+    still current after each call.  E = 100: a ragged last wavefront.  What the device-1 handle computes is what
+    a device-0 handle of the same seed computes."""
+    E = 100
+    torch.cuda.set_device(0)
+
+    def still_on_0(what):
+        assert torch.cuda.current_device() == 0, what
+
+    acts = [torch.rand((E, 11), generator=torch.Generator().manual_seed(t)) for t in range(3)]
+    obs = {}
+    for dev in (1, 0):
+        v = SmartNanogridVecEnv(E, seed=31, device=dev, rng="reference", **KW)
+        still_on_0("create")
+        v.reset_tensors(rng="reference")
+        still_on_0("reset_tensors (reference)")
+        v.reset_tensors(rng="device")
+        still_on_0("reset_tensors (device)")
+        obs[dev] = []
+        for t, a in enumerate(acts):
+            o, _, _ = v.step_tensors(a.to(f"cuda:{dev}"))
+            still_on_0(f"step_tensors {t}")
+            obs[dev].append(o.cpu())
+        v.check_errors()
+        still_on_0("check_errors")
+        blob = v.save_state()
+        still_on_0("save_state")
+        v.load_state(blob)
+        still_on_0("load_state")
+        v.get_scenarios()
+        still_on_0("get_scenarios")
+        g = EpisodeGraph(v, torch.zeros((24, E, 11), device=f"cuda:{dev}"), with_reset=True, days=1)
+        still_on_0("EpisodeGraph capture")
+        g.launch()
+        still_on_0("EpisodeGraph.launch")
+        torch.cuda.synchronize(dev)
+        g.close()
+        still_on_0("EpisodeGraph.close")
+        v.close()
+        still_on_0("close")
+    for t in range(3):
+        assert torch.equal(obs[1][t], obs[0][t]), t
