@@ -1,4 +1,5 @@
-// sng_diag_hooks.h -- the diagnostic hooks of sng_kernels.hip.  In libsng.so every hook is empty.
+// sng_diag_hooks.h -- the diagnostic hooks of the kernels (the headers of sng_kernels.hip; sng_dev_util.h
+// includes this file inside namespace sng).  In libsng.so every hook is empty.
 //
 // The diagnostic builds are separate translation units under tools/diag/ (never shipped): they define
 // SNG_DIAG_STAMPS or SNG_DIAG_MEMFLOOR and then #include sng_kernels.hip, so the product source carries

@@ -1,0 +1,409 @@
+// sng_step_wide.h -- the wide lean step kernel (step_wide_kernel): L lanes per env, every charger's state in
+// registers; the headline station (N = 10, two lanes) and config 5 (N = 50).
+// Needs <type_traits>, sng_dev_util.h (buffer access, TileStage, copy_out, wave_lds_fence), sng_dev_sums.h
+// (PairwiseSum) and sng_dev_env.h (charger_step, bess_step, env_tail, StepConst, ...).  Included by
+// sng_kernels.hip only.
+#pragma once
+
+namespace sng {
+
+// ---------------------------------------------------------------------------------
+// The wide lean step kernel: step_lean_kernel's recipe for stations wider than 16 chargers (BASELINE
+// config 5: N = 50, 15-minute steps, stochastic PV / price profiles), one wavefront per 64 envs, one
+// wavefront per workgroup, one wavefront per SIMD at E = 65,536 (so the whole 512-entry register file:
+// every charger's state is loaded up front).  What makes it lean at N = 50:
+//   - the charging total is the running sum whenever that equals numpy's pairwise sum of the compacted
+//     positive powers exactly (step_lean_kernel's argument: fewer than 8 terms, or float32 powers whose
+//     sum stays below 2^28 times the smallest), instead of numpy's 8-accumulator schedule fed one
+//     power at a time (PairwiseSum: ~40 VALU per power, two per charger);
+//   - the discharging total is exactly 0.0 (numpy's sum of an empty array) when no action of the wave is
+//     negative: a negative power needs a negative action (charger.py:37-56, 108-140), and then no power
+//     is positive other than a charging product.  A wavefront with a negative action (V2X) takes the
+//     general order, PairwiseSum over both signs, in a rolled loop that re-reads each charger's inputs
+//     (rare: nothing in the fast loop indexes the register arrays at run time);
+//   - a lane whose positive sum is not provably exact rebuilds its compacted positive powers from what
+//     the step leaves unchanged -- the records (occupancy) and the actions tile (the float32 product
+//     charger.py:92-94) -- and sums them in numpy's order (rare);
+//   - constants by value, one kernarg round trip before the loads, 1/cap by recip_cap, no LDS but the
+//     actions and observation tiles (40 KB per wavefront: four per CU).
+// ---------------------------------------------------------------------------------
+
+template <int NC, int L>
+struct WideLds {
+    static constexpr int WENVS = kWave / L;   // envs per wavefront
+    static constexpr int A = NC + 1;          // actions per env with a BESS (one fewer without)
+    static constexpr int O = 2 * NC + 9;
+    static constexpr int ACT = round4(WENVS * A), OBS = round4(WENVS * O);
+    static constexpr size_t BYTES = (size_t)(ACT + OBS) * 4;
+};
+
+// Lane `part` K's value of an env's L adjacent lanes (L = 2 or 4), for the env's first lane, by DPP quad
+// permutation (the env's lanes never straddle a quad).
+template <int L, int K>
+__device__ __forceinline__ uint32_t from_part(uint32_t x) {
+    constexpr int ctrl = L == 2 ? (K | (K << 2) | ((K + 2) << 4) | ((K + 2) << 6)) : (K | (K << 2) | (K << 4) | (K << 6));
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, ctrl, 0xF, 0xF, false);
+}
+template <int L, int K>
+__device__ __forceinline__ double from_part(double x) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, x);
+    const uint64_t lo = from_part<L, K>((uint32_t)b), hi = from_part<L, K>((uint32_t)(b >> 32));
+    return __builtin_bit_cast(double, lo | (hi << 32));
+}
+
+// The WENVS = 64 / L envs of a wavefront: their loads (issue), then their step (run).  step_wide_kernel, below,
+// says how the L lanes of an env share its chargers.
+template <int NC, int L, bool PK, bool REQ, bool NOISE>
+struct WideGroup {
+    using Lay = WideLds<NC, L>;
+    static constexpr int WENVS = Lay::WENVS, CPL = (NC + L - 1) / L;
+    static constexpr int KT = (Lay::A * WENVS + 4 * kWave - 1) / (4 * kWave);
+    static_assert((L - 1) * CPL < NC, "every lane steps at least one charger");
+    // The lane's chargers.  Two lanes and N = 2 mod 4 (the headline's 10, config 5's 50): lane `part` steps the
+    // whole charger pairs [part H, part H + H) (H = (N - 2) / 2) and charger N - 2 + part of the last pair, so
+    // its SoC state moves as 16 B charger pairs (sng_layout.h) but for that last charger.  Otherwise the
+    // contiguous ranges [part CPL, min(N, part CPL + CPL)).
+    static constexpr bool kPairs = L == 2 && NC % 4 == 2;
+    // the fast loop's charger step without the discharge branch (charger_step NONNEG) for the headline's
+    // station (step 6.60-6.66 -> 6.53-6.56 us, profiles/r04_ab_nonneg.txt).  At N = 50 the compiler merges
+    // several chargers' select masks ahead of the per-charger scheduling barriers and spills them (332
+    // v_readlane); with each charger's inputs pinned to its block it compiles to 5.5 % fewer VALU, and
+    // config 5 ran 22.62-22.69 against 22.47-22.54 us (profiles/r04_ab_config5_nonneg.txt): its step is
+    // bound by its bytes, so config 5 keeps the general form
+    static constexpr bool kNonneg = NC <= 16;
+    static constexpr int H = (NC - 2) / 2;
+    static_assert(!kPairs || CPL == H + 1, "a lane's chargers: H from whole pairs and one from the last");
+    // the lane's whole pairs are whole record quads too (H a multiple of 4: N = 10, 50), and the last pair is
+    // the partial quad's two records
+    static constexpr bool kQuads = kPairs && H % 4 == 0;
+    static __device__ __forceinline__ int charger(int part, int j) {
+        return kPairs ? (j < H ? part * H + j : NC - 2 + part) : part * CPL + j;
+    }
+    int64_t e0;
+    int nw;
+    bool live;
+    uint32_t el1, el4, el8, row4, row4_last, soc_a, soc_b, rec_a, rec_b;
+    TileStage<KT, kWave> act_tile;
+    double ratio, bess_l, pen0_l, ret_l;
+    double fpv[4], fpr[4];
+    uint32_t w[CPL];
+    double aux[PK ? 1 : CPL], run_[CPL], req[REQ ? CPL : 1];
+    SNG_WSTAMP_DECL;   // diagnostic builds: 0 issue, 1 actions tile staged, 2 chargers, 3 env tail, 4 obs stores issued
+
+    // the (per-lane, uniform) byte offsets of charger j of the lane in a [N][E] u32 plane: j * E in the uniform
+    // part, except for the j some lane lacks (a ragged last lane) or the last pair's charger, where the
+    // per-lane part carries it
+    static __device__ __forceinline__ bool ragged(int j) { return !kPairs && NC % L != 0 && j >= NC - (L - 1) * CPL; }
+    __device__ __forceinline__ uint32_t r4_of(int j, int64_t E) const {
+        if constexpr (kPairs) return (uint32_t)(j < H ? j : NC - 2) * (uint32_t)E * 4u;
+        return ragged(j) ? 0u : (uint32_t)j * (uint32_t)E * 4u;
+    }
+    __device__ __forceinline__ uint32_t row_of(int j, int nc, int64_t E) const {
+        if constexpr (kPairs) return j < H ? row4 : row4_last;
+        return ragged(j) ? (j < nc ? row4 + (uint32_t)j * (uint32_t)E * 4u : row4_last) : row4;
+    }
+    // loads oldest-needed-first: the actions tile and the per-env values, then every charger's state
+    __device__ __forceinline__ void issue(int64_t e0_, const float *act, int64_t E, int t, int vec_io, const Params &p,
+                                          const DeviceState &s, const InfoPtrs &info, int lane) {
+        SNG_WSTAMP(0);
+        const int le = lane / L, part = lane % L;
+        e0 = e0_;
+        nw = (E - e0) < WENVS ? (int)(E - e0) : WENVS;
+        live = le < nw;
+        const int64_t el = live ? e0 + le : E - 1;   // idle lanes load a valid env and discard it
+        el1 = (uint32_t)el;
+        el4 = el1 * 4u;
+        el8 = el1 * 8u;
+        const int c0 = part * CPL;
+        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
+        if constexpr (kPairs) {
+            row4 = el4 + (uint32_t)(part * H) * (uint32_t)E * 4u;     // charger part H + j, j < H: + j E (uniform)
+            row4_last = el4 + (uint32_t)part * (uint32_t)E * 4u;      // charger N - 2 + part: + (N - 2) E (uniform)
+            soc_a = 2u * el8 + (uint32_t)(part * H) * (uint32_t)E * 8u;   // pair row part H + j: + j E 8 (uniform)
+            soc_b = 2u * el8 + (uint32_t)part * 8u;                      // the last pair's row: + (N - 2) E 8
+            rec_a = el1 * 8u + (uint32_t)(part * H) * (uint32_t)E * 2u;   // quad row part H + j: + j E 2 (uniform)
+            rec_b = el1 * 4u + (uint32_t)part * 2u;                      // the partial quad (N - 2, N - 1): + (N - 2) E 2
+        } else {
+            // the lane's first charger row as a per-lane byte offset; charger j of the lane adds j * E
+            // (uniform).  Past the lane's range (j >= nc) the loads re-read its first charger and nothing is
+            // stored.
+            row4 = el4 + (uint32_t)c0 * (uint32_t)E * 4u;
+            row4_last = el4 + (uint32_t)(NC - 1) * (uint32_t)E * 4u;
+        }
+        const size_t plane = (size_t)t * NC * (size_t)E;   // this step's timeline planes
+        const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1
+        const int Ad = p.act_dim;
+        act_tile.issue(act + e0 * Ad, nw * Ad, vec_io != 0, lane);
+        ratio = bld(s.ratio, el8);
+        bess_l = bld(p.bess ? s.bess : s.ratio, el8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fpv[j] = fpr[j] = 1.0;
+        if constexpr (NOISE) profile_factors(p, s, el8, t, fpv, fpr);   // the day's profile factors of t..t+3
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            // charger `charger(part, j)` (past a ragged lane's range: its charger NC - 1 again, discarded)
+            const uint32_t v4 = row_of(j, nc, E), r4 = r4_of(j, E), v8 = 2u * v4, r8 = 2u * r4;
+            if (PK) {   // 2 B records in charger quads: the lane's whole quads as 8 B, its last-pair charger as 2 B
+                if constexpr (kQuads) {
+                    if (j < H && (j & 3) == 0)
+                        unpack_quad(bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)j * (uint32_t)E * 2u),
+                                    w + j);
+                    if (j == H) w[j] = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
+                } else {
+                    const int cr = charger(part, j) < NC ? charger(part, j) : NC - 1;
+                    const RecOff ro = rec_off(cr, NC, E, el1);
+                    w[j] = bld16(rec_t, ro.v, ro.s);
+                }
+            } else {
+                w[j] = bld(s.word + plane, v4, r4);
+                aux[PK ? 0 : j] = bld(s.aux + plane, v8, r8);
+            }
+            if constexpr (kPairs) {   // a pair's 16 B once both its records are issued; the last pair's 8 B
+                if (j < H && (j & 1)) bld2(s.soc, soc_a, (uint32_t)(j - 1) * (uint32_t)E * 8u, run_[j - 1], run_[j]);
+                if (j == H) run_[j] = bld(s.soc, soc_b, (uint32_t)(NC - 2) * (uint32_t)E * 8u);
+            } else {
+                const int c = c0 + j < NC ? c0 + j : NC - 1;
+                run_[j] = bld(s.soc, (uint32_t)soc_index(c, el, NC, E) * 8u);
+            }
+            if (REQ) req[REQ ? j : 0] = bld(s.req + plane, v8, r8);
+        }
+        // the t = 0 penalty and the day return are read only by the env tail: issued behind every charger's
+        // loads, so the waits before the chargers (the header's PV ratio, the BESS step's SoC) do not count them
+        // (round 6, A/B in the day graph: 6.36 -> 6.25-6.29 us per step, profiles/r06_ab_step_tail_order.txt).
+        // Stores issued earlier or in bursts measured slower there: the observation tile stored before the env
+        // tail +0.33 us, its copy-out unrolled (every LDS read, then every 16 B store) +0.6 us, the SoC pairs
+        // stored after the charger loop +0.3 us -- paced stores leave the other wavefronts' loads alone.
+        pen0_l = bld(t == 0 ? s.pen0 : s.ratio, el8);
+        ret_l = bld(info.episode_return ? info.episode_return : s.ratio, el8);
+    }
+    // the requested SoC at python index t-1 of charger j of the lane, or its default without the stream
+    __device__ __forceinline__ double req_of(int j, const Params &p) const {
+        return REQ ? req[REQ ? j : 0] : req_default(p);
+    }
+
+    // the group's step; s_act holds its actions tile (committed), s_obs is the wavefront's observation tile
+    __device__ __forceinline__ void run(const float *s_act, float *s_obs, float *obs, double *reward, uint8_t *done,
+                                        int64_t E, int t, int vec_io, const StepConst &k, const Params &p,
+                                        const DeviceState &s, const InfoPtrs &info, int lane) {
+        SNG_WSTAMP(1);
+        const int Ad = p.act_dim, O = p.obs_dim;
+        const int le = lane / L, part = lane % L;
+        const bool leader = part == 0;
+        const int c0 = part * CPL;
+        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
+        const size_t plane = (size_t)t * NC * (size_t)E;
+        const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;
+        const float *a_row = s_act + le * Ad;
+        float *o_row = s_obs + le * O;
+        float av[CPL];
+        // the largest action bit pattern: above +inf's (0x7f800000) when some action is negative (-0.0 too) or
+        // NaN, and such a wavefront takes the general order below (an integer max keeps no per-charger lane
+        // masks alive into the charger loop)
+        uint32_t amax_bits = 0u;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = charger(part, j);
+            av[j] = a_row[c < NC ? c : NC - 1];
+            amax_bits = __builtin_elementwise_max(amax_bits, __builtin_bit_cast(uint32_t, av[j]));
+        }
+        const bool not_nonneg = amax_bits > 0x7f800000u;
+        const float bess_action = p.bess ? a_row[NC] : 0.0f;
+        const int k_soc = p.pv ? 8 : 4;
+        // the observation header and the BESS step need only per-env values: both run here, while the
+        // chargers' loads are still in flight (the BESS's division no longer trails the charger sums)
+        BessStep bs{};
+        if (live && leader) {
+            write_obs_header(o_row, p, k.v + CST_IRR, k.v + CST_PN, ratio, fpv, fpr);
+            bs = bess_step(p, s, el8, t, p.bess ? bess_l : 0.0, bess_action);
+            if (p.bess) o_row[O - 1] = (float)bs.bess;
+        }
+
+        double pen_v = 0.0, p_ch = 0.0, p_dis = 0.0;
+        uint32_t n_nonexist = 0, fl = 0;
+        if (__builtin_amdgcn_ballot_w64(live && not_nonneg) == 0) {
+            // the fast loop: every action of the wave is >= 0, so no negative power (p_dis stays 0.0) and no
+            // charger discharges (charger_step<..., NONNEG>)
+            double seq_pos = 0.0, pmin = __builtin_inf();
+            int n_pos = 0;
+            double qv[L > 1 ? CPL : 1], sv[CPL];
+            if (live) {
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) {
+                    const int c = charger(part, j);
+                    if (!kPairs && NC % L != 0 && j >= nc) {   // a ragged lane's range ends: adds nothing
+                        qv[L > 1 ? j : 0] = 0.0;
+                        continue;
+                    }
+                    const uint32_t capi = cap_field<PK>(w[j]);
+                    const bool occ = (w[j] & W_OCC) != 0;
+                    const ChargerResult r = charger_step<true, true, kNonneg, PK>(p, PK ? (w[j] & ~W_STATIC) : w[j],
+                                                                           PK ? 0.0 : aux[PK ? 0 : j], run_[j], req_of(j, p),
+                                                                           av[j], t, recip_cap((double)capi));
+                    sv[j] = (PK && !occ) ? (double)rec_soc(w[j]) : r.soc;
+                    if constexpr (kPairs) {   // a pair's 16 B once both its chargers are stepped; the last pair's 8 B
+                        if (j < H && (j & 1))
+                            bst2<kNT>(s.soc, soc_a, sv[j - 1], sv[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
+                        if (j == H) bst<kNT>(s.soc, soc_b, sv[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
+                    } else {
+                        bst<kNT>(s.soc, (uint32_t)soc_index(c, el1, NC, E) * 8u, sv[j]);
+                    }
+                    o_row[k_soc + c] = (float)r.soc;
+                    o_row[k_soc + NC + c] = departure_obs<PK>((PK && !occ) ? 0u : w[j]);
+                    n_nonexist += r.nx;
+                    fl |= r.fl;
+                    if (L > 1) qv[L > 1 ? j : 0] = r.q;
+                    // the lane's own penalties in charger order; kPairs: the last pair's come after the other
+                    // lane's whole pairs (gather, below)
+                    if (!kPairs || j < H) pen_v += r.q;
+                    const bool ip = r.pw > 0.0;
+                    seq_pos += r.pw;   // >= 0 here (the float32 product of a >= 0, or 0.0): adding it is exact
+                    n_pos += ip ? 1 : 0;
+                    pmin = __builtin_fmin(pmin, ip ? r.pw : __builtin_inf());
+                    // chargers in order: charger j waits only for its own loads.  A/B of scheduling groups
+                    // (profiles/r03_ab_wide_sched_groups.txt): config 5 22.6-22.7 us with one or two chargers
+                    // per group, 22.8 with five, 27.1 with no barrier in a lane's 25 chargers; the headline
+                    // within noise
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            // numpy sums fewer than 8 positive powers in order: one lane's running sum is that sum; two lanes'
+            // partial sums combined are that sum only when one of them is empty or the sum is exact
+            bool split = false;
+            if constexpr (L > 1) {
+                // the other lanes' totals (exact combinations), and their penalties after the first lane's own,
+                // in charger order (adding a +0.0 term is exact)
+                const double seq_own = seq_pos, pmin_own = pmin;
+                const int n_own = n_pos;
+                const uint32_t nx_own = n_nonexist, fl_own = fl;
+                int with_pos = n_own > 0 ? 1 : 0;
+                auto gather = [&](auto kc) {
+                    constexpr int K = decltype(kc)::value;
+                    const int nk = (int)from_part<L, K>((uint32_t)n_own);
+                    with_pos += nk > 0 ? 1 : 0;
+                    n_pos += nk;
+                    seq_pos += from_part<L, K>(seq_own);
+                    pmin = __builtin_fmin(pmin, from_part<L, K>(pmin_own));
+                    n_nonexist += from_part<L, K>(nx_own);
+                    fl |= from_part<L, K>(fl_own);
+#pragma unroll
+                    for (int j = 0; j < (kPairs ? H : CPL); ++j) {
+                        const double qk = from_part<L, K>(qv[L > 1 ? j : 0]);
+                        pen_v = leader ? pen_v + qk : pen_v;
+                    }
+                };
+                gather(std::integral_constant<int, 1>{});
+                if constexpr (L > 2) {
+                    gather(std::integral_constant<int, 2>{});
+                    gather(std::integral_constant<int, 3>{});
+                }
+                if constexpr (kPairs) {   // the last pair: charger N - 2 (this lane), then N - 1 (the other)
+                    const double qk = from_part<L, 1>(qv[L > 1 ? H : 0]);
+                    pen_v = leader ? (pen_v + qv[L > 1 ? H : 0]) + qk : pen_v;
+                }
+                split = with_pos > 1;
+            }
+            p_ch = seq_pos;
+            const bool pos_slow = live && leader && (n_pos >= 8 || split) && !(seq_pos <= pmin * 0x1.0p28);
+            if (__builtin_amdgcn_ballot_w64(pos_slow)) {   // wave-uniform: rare
+                if (pos_slow) {
+                    // the compacted positive powers again, in charger order: an occupied charger charging with
+                    // a > 0 under bounded charging bills pc (charger.py:58-94); nothing else is positive here
+                    PairwiseSum pos;
+                    pos.init();
+#pragma unroll 1
+                    for (int c = 0; c < NC; ++c) {
+                        const RecOff ro = rec_off(c, NC, E, el1);
+                        const uint32_t wc = PK ? bld16(rec_t, ro.v, ro.s)
+                                               : bld(s.word + plane, el4, (uint32_t)c * (uint32_t)E * 4u);
+                        const float a = a_row[c];
+                        const double pc = charging_power(p, a);
+                        if ((wc & W_OCC) && p.bounded && a > 0.0f && pc > 0.0) pos.push(pc);
+                    }
+                    p_ch = pos.result();
+                }
+            }
+        } else {
+            // a wave with a discharging action: numpy's pairwise order for both signs (PairwiseSum), one
+            // charger at a time on the env's first lane, its inputs re-read from memory and the actions tile
+            PairwiseSum pos, neg;
+            pos.init();
+            neg.init();
+            if (live && leader) {
+#pragma unroll 1
+                for (int c = 0; c < NC; ++c) {
+                    const uint32_t r4 = (uint32_t)c * (uint32_t)E * 4u, r8 = 2u * r4;
+                    const SocOff so = soc_off(c, NC, E, el8);
+                    const RecOff ro = rec_off(c, NC, E, el1);
+                    const uint32_t wc = PK ? bld16(rec_t, ro.v, ro.s) : bld(s.word + plane, el4, r4);
+                    const double auxc = PK ? 0.0 : bld(s.aux + plane, el8, r8);
+                    const double runc = bld(s.soc, so.v, so.s);
+                    const double reqc = REQ ? bld(s.req + plane, el8, r8) : req_default(p);
+                    const uint32_t capi = cap_field<PK>(wc);
+                    const bool occ = (wc & W_OCC) != 0;
+                    const ChargerResult r = charger_step<true, true, false, PK>(p, PK ? (wc & ~W_STATIC) : wc, auxc, runc,
+                                                                                reqc, a_row[c], t, recip_cap((double)capi));
+                    bst<kNT>(s.soc, so.v, (PK && !occ) ? (double)rec_soc(wc) : r.soc, so.s);
+                    o_row[k_soc + c] = (float)r.soc;
+                    o_row[k_soc + NC + c] = departure_obs<PK>((PK && !occ) ? 0u : wc);
+                    n_nonexist += r.nx;
+                    fl |= r.fl;
+                    pen_v += r.q;
+                    if (r.pw > 0.0) pos.push(r.pw);
+                    if (r.pw < 0.0) neg.push(r.pw);
+                }
+            }
+            p_ch = pos.result();
+            p_dis = neg.result();
+        }
+        SNG_WSTAMP(2);
+        if (live && leader) {
+            pen_v += (t == 0) ? pen0_l : 0.0;   // python index -1 slot; every per-charger term is 0 at t = 0
+            env_tail<false, true>(p, s, info, e0, (uint32_t)le, el1, el8, t, ratio, p.bess ? bess_l : 0.0, bess_action,
+                                  p_ch, p_dis, pen_v, 100.0 * (double)n_nonexist, fl, o_row, k.v, fpv, fpr,
+                                  info.episode_return ? ret_l : 0.0, 0.0, reward, done, &bs);
+        }
+        SNG_WSTAMP(3);
+        wave_lds_fence();
+        copy_out<kWave>(obs + e0 * O, s_obs, nw * O, vec_io != 0, lane);
+        SNG_WSTAMP(4);
+    }
+};
+
+// L lanes per env (1, 2 or 4): lane `part` of an env steps chargers [part * CPL, min(NC, (part + 1) * CPL)),
+// CPL = ceil(NC / L).  The env's lanes are adjacent (one DPP quad); the partial charging sums, counts and
+// minima combine exactly on the first lane (a sum the exactness test accepts is exact in any order, and
+// fewer than 8 powers are numpy's in-order sum when one lane holds them all), the first lane adds the
+// other lanes' vehicle penalties after its own in charger order (Python's sum, penaliser.py:55), and the
+// rare exact-order paths run on the first lane over all chargers.  One group of 64 / L envs per wavefront;
+// the register budget is sized for L waves per SIMD (every wave of the E = 65,536 grid resident at once).
+// Measured and reverted (A/B on one box):
+//   - two groups of 32 envs per wavefront at N = 10 (1,024 wavefronts, each group's loads issued before the
+//     first group is stepped): 8.62-8.64 us per step in the graph against 6.68-6.71 us
+//     (profiles/r04_ab_groups.txt);
+//   - config 5 with four lanes per env and a 3-wave budget (166 VGPRs, no spills, 3 of the 4,096 waves per
+//     SIMD resident): 29.6-29.8 us against 23.4 us with two lanes (profiles/r03_ab_config5_four_lanes.txt);
+//   - round 5: two or four such wavefronts per workgroup (each with its own envs and LDS tiles, no barrier;
+//     512 / 1,024 workgroups instead of 2,048): 6.79-6.80 / 6.99-7.03 us per step in the graph against
+//     6.31-6.34 us with one (profiles/r05_ab_waves_per_workgroup.txt).
+template <int NC, int L, bool PK, bool REQ, bool NOISE>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) void
+step_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *__restrict__ reward,
+                 uint8_t *__restrict__ done, int64_t E, int t, int vec_io, StepConst k, Params p, DeviceState s,
+                 InfoPtrs info) {
+    static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per env");
+    using Grp = WideGroup<NC, L, PK, REQ, NOISE>;
+    using Lay = WideLds<NC, L>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x;
+    float *s_obs = lds + Lay::ACT;   // the actions tile, then the observation tile
+    Grp g;
+    const int64_t e0 = (int64_t)blockIdx.x * Grp::WENVS;   // the grid covers E: the wavefront has an env
+    g.issue(e0, act, E, t, vec_io, p, s, info, lane);
+    g.act_tile.commit(lds, lane);
+    wave_lds_fence();
+    g.run(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
+    SNG_WSTAMP_FLUSH(g.stamp_, 5);
+    bump_day_counter<PK>(p, s, t);
+}
+
+}  // namespace sng

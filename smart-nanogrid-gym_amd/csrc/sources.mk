@@ -1,7 +1,9 @@
 # The library's sources and its build id, shared by csrc/Makefile and tools/diag/Makefile (tools/diag/variant.sh
 # copies csrc/ whole, so this fragment travels with a variant's sources).
 SNG_SRCS := sng_kernels.hip sng_api.cpp sng_comm.cpp
-SNG_HDRS := sng_layout.h sng_mt.h sng_diag_hooks.h sng_launch.h sng_step_plan.h sng_device_scope.h
+# every header of the directory this fragment lies in, sorted: a new header is in the build id and in make's
+# dependencies without being listed anywhere
+SNG_HDRS := $(sort $(notdir $(wildcard $(dir $(lastword $(MAKEFILE_LIST)))*.h)))
 # $(call sng_build_id,<csrc directory>,<compile flags>): the first 12 hex digits of the SHA-256 of every source
 # of the library, the compile flags and the compiler's version line (the same sources built with
 # other flags or another ROCm are another binary).  The committed measurements under profiles/ are keyed by

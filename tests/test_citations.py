@@ -35,7 +35,7 @@ CONTENT_EXCEPTIONS = {
         "PVSystem(...)'s parameters at :17 give scaling_pv (the local of :68)",
     ("smart-nanogrid-gym_amd/csrc/sng_api.cpp", "charging_station.py", 200):
         "the generator body; clear_initialisation_variables is cited separately (:138-150)",
-    ("smart-nanogrid-gym_amd/csrc/sng_kernels.hip", "charging_station.py", 230):
+    ("smart-nanogrid-gym_amd/csrc/sng_dev_env.h", "charging_station.py", 230):
         "the requested-SoC default 1.0 of the generator; the Requested_SOC key is the dict's",
     ("smart-nanogrid-gym_amd/smart_nanogrid_gym/vec_env.py", "charging_station.py", 164):
         "the dict literal generated_initial_values(_json): the initial_values file it is written to",

@@ -1,4 +1,4 @@
-"""GPU: the lean step kernel's charging / discharging totals (csrc/sng_kernels.hip, step_lean).
+"""GPU: the lean step kernel's charging / discharging totals (csrc/sng_step_lean.h, step_lean_kernel).
 
 The lean step (N <= 16, one lane per env, no diagnostics, NumPy-2 promotion, power-of-two dt) keeps the
 running sums of the positive and negative charger powers and uses them as numpy's pairwise sums of the

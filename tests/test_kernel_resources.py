@@ -4,7 +4,7 @@ libsng.so ships (AMDHSA metadata: .vgpr_count, .agpr_count, .sgpr_count, .privat
 
 Several measured numbers depend on how many wavefronts of a kernel share a SIMD, and that is set by the
 compiler's register allocation, not by the source alone:
-  - ref_day2_kernel reserves v175 (`asm volatile("v_mov_b32 v175, 0" ::: "v175")`, sng_kernels.hip) so its
+  - ref_day2_kernel reserves v175 (`asm volatile("v_mov_b32 v175, 0" ::: "v175")`, sng_ref_day.h) so its
     VGPR count is above 512 / 3 and it runs at most two wavefronts per SIMD: 86.9 -> 77.5 us of span
     (profiles/r05_ab_refday_two_wavefronts.txt).  A toolchain that allocated differently, or dropped the
     clobber, would silently bring back the three-per-SIMD placement.

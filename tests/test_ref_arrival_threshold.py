@@ -1,4 +1,4 @@
-"""CPU: the integer arrival test of ref_day2_kernel (sng_kernels.hip kArrive53) against the reference's
+"""CPU: the integer arrival test of ref_day2_kernel (sng_ref_day.h kArrive53) against the reference's
 double expression round(random.rand() - 0.1) == 1 (charging_station.py:214-215).
 
 random.rand() is numpy's rk_double, K / 2^53 with K = (a >> 5) << 26 | (b >> 6) from two tempered words;
@@ -10,12 +10,12 @@ from pathlib import Path
 
 import numpy as np
 
-KERNELS = Path(__file__).resolve().parents[1] / "smart-nanogrid-gym_amd" / "csrc" / "sng_kernels.hip"
+KERNELS = Path(__file__).resolve().parents[1] / "smart-nanogrid-gym_amd" / "csrc" / "sng_ref_day.h"
 
 
 def _threshold():
     m = re.search(r"constexpr uint64_t kArrive53 = (0x[0-9a-fA-F]+)ull;", KERNELS.read_text())
-    assert m, "kArrive53 not found in sng_kernels.hip"
+    assert m, "kArrive53 not found in sng_ref_day.h"
     return int(m.group(1), 16)
 
 

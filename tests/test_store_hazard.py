@@ -6,7 +6,7 @@ ROCm 7.2's LLVM inserts that wait for FLAT/global stores and for MUBUF stores wh
 constant, but not for MUBUF stores with an SGPR soffset, which it believes safe.  On gfx950 they are not:
 round 4's first SoC-pair build lost the high dword of ~0.1 % of the stored SoC slots at 65,536 envs to a
 v_cvt_f32_ubyte2 that overwrote the pair right after its store (134 such pairs in the library).  Every wide
-raw-buffer store now passes a literal 0 soffset (bst2, sng_kernels.hip), and this test disassembles the
+raw-buffer store now passes a literal 0 soffset (bst2, sng_dev_util.h), and this test disassembles the
 gfx950 code object the library ships -- compiler-emitted stores included -- and finds every wide store
 followed, within its wait states and before any branch, by a VALU writing one of its data VGPRs.
 

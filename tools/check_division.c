@@ -1,4 +1,4 @@
-/* Exhaustive check of the two fma-based divisions in the step kernel (sng_kernels.hip).
+/* Exhaustive check of the two fma-based divisions in the step kernels (csrc/sng_dev_env.h).
  *
  * 1. div_by_cap: for float32-valued x and integer c in [1, 255], r = fl(1/c),
  *        q = x*r;  q' = fma(fma(-q, c, x), r, q)   ==   x / c   (IEEE float64)

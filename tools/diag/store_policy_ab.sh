@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the state stores' cache policy (SoC pairs, BESS, day return, flags: bst / bst2 in sng_kernels.hip) on the
+# A/B of the state stores' cache policy (SoC pairs, BESS, day return, flags: bst / bst2 in csrc/sng_dev_util.h) on the
 # headline day: libsng (nt), libsng_wt (sc0 | sc1 | nt: written through at system scope), libsng_wt1 (sc0 | sc1),
 # built by tools/diag/variant.sh.  Why: without an agent-scope release a next kernel on another XCD reads stale
 # lines (profiles/r06_coherence_probe.txt), so every step ends with an L2 writeback of what it left dirty.

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B library of the current source with one edit (never shipped):
-#   tools/diag/variant.sh <name> <sed expression on sng_kernels.hip>  ->  lib/libsng_<name>.so
+#   tools/diag/variant.sh <name> <sed expression on csrc/sng_kernels.hip and csrc/*.h>  ->  lib/libsng_<name>.so
 #   tools/diag/variant.sh <name> -p <patch against csrc/ (-p1)>         ->  lib/libsng_<name>.so
 # e.g. tools/diag/variant.sh w4 's/wide_wpb(int) { return 1; }/wide_wpb(int) { return 4; }/'
 #      tools/diag/variant.sh refold -p tools/diag/patches/ref_day2_one_wave.patch
@@ -16,7 +16,7 @@ cp -r "$ROOT/smart-nanogrid-gym_amd/csrc" "$tmp/csrc"
 if [ "$1" = "-p" ]; then
   patch -s -p1 -d "$tmp/csrc" < "$(realpath "$2")"
 else
-  sed -i "$1" "$tmp/csrc/sng_kernels.hip"
+  sed -i "$1" "$tmp/csrc/sng_kernels.hip" "$tmp"/csrc/*.h   # the kernels live in the headers it includes
 fi
 if diff -rq "$tmp/csrc" "$ROOT/smart-nanogrid-gym_amd/csrc" > /dev/null; then
   echo "variant.sh: the edit changed nothing" >&2; rm -rf "$tmp"; exit 2
