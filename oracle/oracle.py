@@ -81,6 +81,14 @@ def lib():
         L.orc_pairwise_sum.argtypes = [dp, ctypes.c_long]
         L.orc_run_batch.restype = d
         L.orc_run_batch.argtypes = [vp, i64, u64, i, fp, i64, fp]
+        L.orc_device_day.restype = i
+        L.orc_device_day.argtypes = [vp, u64, u64, u64, ip, i, dp, dp, dp, dp, ip, ip, i, dp, ip]
+        L.orc_device_ratio.restype = d
+        L.orc_device_ratio.argtypes = [u64, u64, u64]
+        L.orc_device_replay_ratio.restype = d
+        L.orc_device_replay_ratio.argtypes = [u64, u64, u64]
+        L.orc_device_wait_census.restype = i
+        L.orc_device_wait_census.argtypes = []
         _lib = L
     return _lib
 
@@ -234,6 +242,50 @@ class OracleEnv:
         fpv, fpr = np.zeros(n), np.zeros(n)
         lib().orc_env_get_profiles(self.ptr, _ptr(fpv, ctypes.c_double), _ptr(fpr, ctypes.c_double))
         return fpv, fpr
+
+
+def device_day(cfg, seed, ge, day, follow=None, vmax=8):
+    """The device-RNG day the GPU generator must write for global env `ge` on day number `day` of a handle
+    seeded `seed` (orc_device_day in sng_oracle.c: a CPU model of the generator's streams, exact but for the
+    geometric wait's two-candidate rule).  follow: the GPU's exported arrivals of that env, [N][V] padded with
+    -1, which settle ambiguous waits; None takes floor(x).
+
+    Returns OracleEnv.scenario()'s arrays (soc, occ, cap, req [N][slots]; arrivals, departures [N][vmax],
+    -1 padded) and `ratio` (the day's PV ratio), `vehicles`, `ambiguous` (ambiguous draws met) and `followed`
+    (ambiguous draws where the GPU's arrival was one of the two candidates)."""
+    N, S = cfg.N, cfg.slots
+    soc, occ, cap, req = (np.empty((N, S)) for _ in range(4))
+    arr = np.empty((N, vmax), np.int32)
+    dep = np.empty((N, vmax), np.int32)
+    ratio = np.zeros(1)
+    counts = np.zeros(3, np.int32)
+    fptr, fv = None, 0
+    if follow is not None:
+        follow = np.ascontiguousarray(np.asarray(follow, np.int32).reshape(N, -1))
+        fptr, fv = _ptr(follow, ctypes.c_int), follow.shape[1]
+    most = lib().orc_device_day(cfg.ptr, int(seed), int(ge), int(day), fptr, fv, _ptr(soc, ctypes.c_double),
+                                _ptr(occ, ctypes.c_double), _ptr(cap, ctypes.c_double), _ptr(req, ctypes.c_double),
+                                _ptr(arr, ctypes.c_int), _ptr(dep, ctypes.c_int), vmax, _ptr(ratio, ctypes.c_double),
+                                _ptr(counts, ctypes.c_int))
+    if most < 0:
+        raise ValueError(f"oracle: a charger's day holds more than {vmax} vehicles")
+    return dict(soc=soc, occ=occ, cap=cap, req=req, arrivals=arr, departures=dep, ratio=float(ratio[0]),
+                vehicles=int(counts[0]), ambiguous=int(counts[1]), followed=int(counts[2]))
+
+
+def device_ratio(seed, ge, day):
+    """PV ratio of device day `day` (pv_ratio_draw)."""
+    return lib().orc_device_ratio(int(seed), int(ge), int(day))
+
+
+def device_replay_ratio(seed, ge, replay):
+    """PV ratio a replayed device day redraws: replay number `replay` of the handle (replay_ratio_draw)."""
+    return lib().orc_device_replay_ratio(int(seed), int(ge), int(replay))
+
+
+def device_wait_census():
+    """How many of the 2^24 values of the wait's uniform draw are ambiguous at the model's margin."""
+    return lib().orc_device_wait_census()
 
 
 class OracleRng:

@@ -10,6 +10,9 @@
  * and against the reference's recorded PPO episodes (tests/golden/kat/<file>.json).
  * The RNG restatement is checked draw-for-draw against numpy.random.RandomState
  * and Python's random.Random (tests/test_oracle_rng.py).
+ * The model of a device-RNG day (orc_device_day, near the end) is checked against this file's own
+ * reference generator in law (tests/test_device_day_model_cpu.py) and is what the GPU generator's
+ * days must equal (tests/test_gpu_device_day_exact.py).
  *
  * It is a scalar, per-environment restatement that keeps the reference's own data
  * structures (25-slot per-charger arrays, ragged arrival/departure lists, the
@@ -154,7 +157,7 @@ int64_t orc_py_randint(orc_mt *s, int64_t a, int64_t b) {
 #define ORC_MAXSLOTS (ORC_MAXT + 1)
 
 /* triple32 integer hash and the stream key shared with the GPU generator
- * (smart-nanogrid-gym_amd/csrc/sng_kernels.hip: mix32, stream_key). */
+ * (smart-nanogrid-gym_amd/csrc/sng_dev_env.h: mix32, stream_key). */
 static uint32_t mix32(uint32_t x) {
     x ^= x >> 17; x *= 0xed5ad4bbu;
     x ^= x >> 11; x *= 0xac4c1b51u;
@@ -829,6 +832,166 @@ void orc_env_get_scenario(const orc_env *e, double *soc, double *occ, double *ca
 void orc_env_get_profiles(const orc_env *e, double *f_pv, double *f_price) {
     memcpy(f_pv, e->f_pv, sizeof(double) * (e->cfg->T + 3));
     memcpy(f_price, e->f_price, sizeof(double) * (e->cfg->T + 3));
+}
+
+/* ------------------------------------------------------------------------------
+ * Device-RNG days: a CPU model of what the GPU generator (generate_kernel, observe_day0) must write.
+ *
+ * A device day is a pure function of (handle seed, global env, charger, day, station settings): the contract
+ * is stated by the comments of smart-nanogrid-gym_amd/csrc/sng_generate.h and sng_layout.h, and restated here
+ * in this file's own shape -- a loop over one charger's vehicles, then plain per-step slot arrays and ragged
+ * arrival / departure lists.  Nothing of the kernel's vehicle list, its sentinel or its branch-free timeline
+ * walk is mirrored, so the two are independent statements of one contract.
+ *
+ *   stream    draw i of charger c is mix32_gen(gen_key(seed, ge, c, day) + i * 0x9e3779b9), "lowbias32";
+ *             gen_key hashes the index ge * 128 + c into the day's seed hash k0, offset by ge >> 25
+ *   vehicle   two draws x1, x2, then a third only with requested SoC enabled:
+ *               wait      failed Bernoulli(0.4) trials before the arrival, floor(log2(u) / log2(0.6)) with
+ *                         u = ((x1 >> 8) + 1) * 2^-24 in (0, 1]: arrival = tfree + wait
+ *               SoC       code = x2 >> 19 (13 bits), value 0.1f + 0.8f * ((code + 0.5) * 2^-13) in float32
+ *               r         ((x1 & 0xff) << 8) | (x2 & 0xff); capacity 15 + (r * 105 >> 16), or 40 when fixed
+ *               departure low + (y * (high - low) >> 16), y = the low 16 bits of r * 105 (of r itself with
+ *                         fixed capacities), low = arrival + i4, high = min(arrival + i10, T + i1); low when
+ *                         the window is empty (charging_station.py:271-279)
+ *               request   lo + (1 - lo) * draw * 2^-32, lo = soc + 0.1 (1.0 above 0.9), in float64
+ *             the day ends with the first arrival at or past T; tfree = departure + 1 (the departure step
+ *             stays empty, charging_station.py:239-251); i4 = int(4 / dt), i10 = int(10 / dt), i1 = int(1 / dt)
+ *   ratio     randint(0, 180) / 100 from the first draw of stream_key(seed, ge, domain, day | replay)
+ *
+ * The wait is the one float operation the GPU takes from a hardware approximation ((int)(__log2f(u) *
+ * kInvLog2Q) in float32).  Here x = log2(u) * (double)kInvLog2Q in float64.  The hardware log2 is within
+ * 1 ulp of the true value (|log2 u| < 32: ulp <= 2^-19, times 1.357 = 2.6e-6) and the float32 product adds
+ * half an ulp of a value below 64 (2^-19 = 1.9e-6), so the GPU's product is within 4.5e-6 of x: a draw is
+ * AMBIGUOUS when an integer lies within ORC_WAIT_MARGIN = 1e-5 of x (342 of the 2^24 values of u, 2.0e-5;
+ * u = 1 is exact on both sides and never ambiguous).  An ambiguous draw has two candidate waits, floor(x)
+ * and its neighbour across that integer.  With `follow` (the arrivals the GPU exported for the charger) the
+ * model takes the GPU's arrival when it is one of the two candidates and floor(x) otherwise, so a real
+ * mismatch still shows; without it, floor(x).  Everything after the wait is integer or exact float64
+ * arithmetic and has one answer.
+ * ---------------------------------------------------------------------------- */
+#define ORC_WAIT_MARGIN 1e-5
+#define ORC_DOMAIN_RATIO 0x7a710000u
+#define ORC_DOMAIN_REPLAY 0x7a720000u
+static const float gen_inv_log2_q = -1.3569154488567239f;   /* 1 / log2(0.6) as the float32 the GPU multiplies by */
+
+static uint32_t mix32_gen(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+static uint32_t gen_key(uint64_t seed, uint64_t ge, uint32_t c, uint64_t day) {
+    uint32_t k0 = mix32((uint32_t)seed ^ mix32((uint32_t)(seed >> 32) + (uint32_t)day * 0x9e3779b9u));
+    uint32_t index = ((uint32_t)ge << 7) | c;             /* ge * 128 + c, mod 2^32 */
+    return mix32((k0 + (uint32_t)(ge >> 25) * 0x85ebca6bu) ^ index);
+}
+
+/* floor wait of draw x1; *amb: an integer lies within the margin of x; *alt: the other candidate (-1: none,
+ * the integer is 0 and a wait cannot be negative) */
+static int gen_wait(uint32_t x1, int *alt, int *amb) {
+    double u = ((double)(x1 >> 8) + 1.0) * 0x1.0p-24;
+    double x = log2(u) * (double)gen_inv_log2_q;
+    double n = floor(x + 0.5);
+    int w = (int)floor(x);
+    *amb = u != 1.0 && fabs(x - n) <= ORC_WAIT_MARGIN;
+    *alt = -1;
+    if (*amb) *alt = (int)n > w ? (int)n : w - 1;
+    return w;
+}
+
+/* ambiguous values among all 2^24 values of u (the margin's own check) */
+int orc_device_wait_census(void) {
+    int count = 0, alt, amb;
+    for (uint32_t k = 0; k < (1u << 24); k++) {
+        (void)gen_wait(k << 8, &alt, &amb);
+        count += amb;
+    }
+    return count;
+}
+
+static float gen_code_soc(uint32_t code) {
+    volatile float u = ((float)code + 0.5f) * (1.0f / 8192.0f);
+    volatile float v = 0.8f * u;
+    return 0.1f + v;
+}
+
+static double ratio_draw(uint64_t seed, uint64_t ge, uint32_t domain, uint64_t index) {
+    uint32_t h = mix32(stream_key(seed, ge, domain, index));
+    return (double)(int)(((uint64_t)h * 181u) >> 32) / 100;
+}
+
+double orc_device_ratio(uint64_t seed, uint64_t ge, uint64_t day) { return ratio_draw(seed, ge, ORC_DOMAIN_RATIO, day); }
+double orc_device_replay_ratio(uint64_t seed, uint64_t ge, uint64_t replay) {
+    return ratio_draw(seed, ge, ORC_DOMAIN_REPLAY, replay);
+}
+
+/* The day of global env `ge`, day number `day`, of a handle seeded `seed`, in orc_env_get_scenario's layout
+ * (slot arrays [N][slots], lists [N][vmax] padded with -1).  follow: NULL, or the GPU's exported arrivals
+ * [N][follow_v] (-1 padded).  counts[0] = vehicles, counts[1] = ambiguous draws met, counts[2] = ambiguous
+ * draws settled by `follow` (the GPU's arrival was one of the two candidates).  Returns the largest vehicle
+ * count of a charger, or -1 when a list does not fit vmax. */
+int orc_device_day(const orc_cfg *c, uint64_t seed, uint64_t ge, uint64_t day, const int *follow, int follow_v,
+                   double *soc, double *occ, double *cap, double *req, int *arrivals, int *departures, int vmax,
+                   double *ratio, int *counts) {
+    int N = c->n_chargers, T = c->T, S = c->slots, most = 0;
+    int i4 = (int)(4 / c->dt), i10 = (int)(10 / c->dt), i1 = (int)(1 / c->dt);
+    memset(soc, 0, sizeof(double) * N * S); memset(occ, 0, sizeof(double) * N * S);
+    memset(cap, 0, sizeof(double) * N * S); memset(req, 0, sizeof(double) * N * S);
+    for (int i = 0; i < N * vmax; i++) arrivals[i] = departures[i] = -1;
+    counts[0] = counts[1] = counts[2] = 0;
+    for (int i = 0; i < N; i++) {
+        uint32_t key = gen_key(seed, ge, (uint32_t)i, day), ctr = 0;
+        int tfree = 0, nv = 0;
+        while (tfree < T) {
+            uint32_t x1 = mix32_gen(key + (ctr++) * 0x9e3779b9u);
+            uint32_t x2 = mix32_gen(key + (ctr++) * 0x9e3779b9u);
+            int alt, amb;
+            int wait = gen_wait(x1, &alt, &amb);
+            if (amb) {
+                counts[1]++;
+                if (follow) {
+                    /* the GPU's v-th arrival, or "none" (its day ended): the candidate that says the same */
+                    int theirs = nv < follow_v ? follow[i * follow_v + nv] : -1;
+                    int cand[2] = {wait, alt};
+                    for (int k = 0; k < 2; k++) {
+                        if (cand[k] < 0) continue;
+                        int ta = tfree + cand[k];
+                        if ((ta < T && theirs == ta) || (ta >= T && theirs < 0)) { wait = cand[k]; counts[2]++; break; }
+                    }
+                }
+            }
+            int ta = tfree + wait;
+            if (ta >= T) break;
+            double s = (double)gen_code_soc(x2 >> 19);
+            uint32_t r = ((x1 & 0xffu) << 8) | (x2 & 0xffu);
+            uint32_t rc = r * 105u;
+            double capacity = c->diff_caps ? (double)(15u + (rc >> 16)) : 40.0;
+            uint32_t y = (c->diff_caps ? rc : r) & 0xffffu;
+            int low = ta + i4;
+            int high = ta + i10 < T + i1 ? ta + i10 : T + i1;
+            int dep = low >= high ? low : low + (int)((y * (uint32_t)(high - low)) >> 16);
+            double request = 1.0;
+            if (c->req_enabled) {
+                uint32_t x3 = mix32_gen(key + (ctr++) * 0x9e3779b9u);
+                double lo = s <= 0.9 ? s + 0.1 : 1.0;
+                request = lo + (1.0 - lo) * ((double)x3 * 0x1.0p-32);
+            }
+            if (nv >= vmax) return -1;
+            arrivals[i * vmax + nv] = ta;
+            departures[i * vmax + nv] = dep;
+            nv++;
+            soc[i * S + ta] = s;
+            for (int t = ta; t < dep && t < T; t++) {
+                occ[i * S + t] = 1; cap[i * S + t] = capacity; req[i * S + t] = request;
+            }
+            tfree = dep + 1;
+        }
+        counts[0] += nv;
+        if (nv > most) most = nv;
+    }
+    *ratio = ratio_draw(seed, ge, ORC_DOMAIN_RATIO, day);
+    return most;
 }
 
 /* RNG probes for the draw-for-draw tests against numpy / Python's random. */

@@ -436,6 +436,56 @@ def test_step_host_batches_equal_step(E, N):
     b_env.close()
 
 
+@pytest.mark.parametrize("E,N,extra", [(100, 10, dict(vehicle_to_everything=True)), (70, 3, dict(charging_mode=""))])
+def test_step_host_batches_report_raised_flags(E, N, extra):
+    """sng_step_host's flag section with flags raised -- V2X breakpoints (central_management_system.py:160-165) and
+    the charging-mode ValueError (charger.py:88) -- over a batch with a ragged last wavefront: after every step the
+    returned per-env flags equal those a twin handle reports through sng_step with info=True (SngInfo.flags), and
+    both handles' sticky flags (sng_read_errors) are the OR of the steps so far."""
+    from smart_nanogrid_gym import _native
+    kw = dict(number_of_chargers=N, time_interval="1h", charging_mode="bounded",
+              vehicle_uncharged_penalty_mode="dense")
+    kw.update(extra)
+    a_env = SmartNanogridVecEnv(E, seed=8, rng="reference", info=True, **kw)
+    b_env = SmartNanogridVecEnv(E, seed=8, rng="reference", **kw)
+    a_env.reset_tensors()
+    b_env.reset_tensors()
+    rng = np.random.default_rng(E)
+    lo, hi = a_env.action_space.low, a_env.action_space.high
+    obs = np.zeros((E, a_env.obs_dim), np.float32)
+    rew = np.zeros(E)
+    done = np.zeros(E, np.uint8)
+    flags = np.zeros(E, np.uint32)
+    sticky = np.zeros(E, np.uint32)
+    P = lambda x: ctypes.c_void_p(x.ctypes.data)   # noqa: E731
+    U = ctypes.POINTER(ctypes.c_uint32)
+
+    def read_sticky(env):
+        out = np.zeros(E, np.uint32)
+        _native.check(_native.lib().sng_read_errors(env._h, out.ctypes.data_as(U), 0, ctypes.c_void_p(0)), env._h)
+        return out
+    want = _native.FLAG_V2X_BREAKPOINT if "vehicle_to_everything" in extra else _native.FLAG_CHARGING_MODE
+    mixed = 0
+    for t in range(a_env.timesteps):
+        act = (lo + (hi - lo) * rng.random((E, lo.size))).astype(np.float32)
+        act[rng.random(act.shape) < 0.5] = 0
+        a_env.step_tensors(torch.from_numpy(act).to(a_env.device))
+        flags[:] = 0xdead   # the call writes every env's slot
+        _native.check(_native.lib().sng_step_host(b_env._h, P(act), P(obs), P(rew), P(done), P(flags),
+                                                  ctypes.byref(b_env._info), ctypes.c_void_p(0)), b_env._h)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(flags, a_env.flags_d.cpu().numpy().astype(np.uint32), err_msg=f"t {t}")
+        assert not (flags & ~np.uint32(want)).any()
+        sticky |= flags
+        np.testing.assert_array_equal(read_sticky(b_env), sticky, err_msg=f"t {t}: sticky flags, host path")
+        np.testing.assert_array_equal(read_sticky(a_env), sticky, err_msg=f"t {t}: sticky flags, device path")
+        mixed += int(0 < np.count_nonzero(flags) < E)
+    # flags were raised per env, not per batch: in both wavefronts, the ragged one included
+    assert mixed > 0 and (sticky[:64] == want).any() and (sticky[64:] == want).any()
+    a_env.close()
+    b_env.close()
+
+
 def test_step_tensors_converts_its_input():
     """step_tensors takes host, float64 and non-contiguous actions (converted to a contiguous float32 device tensor)
     and refuses a wrong shape; every form steps to the same day."""
