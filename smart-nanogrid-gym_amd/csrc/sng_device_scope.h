@@ -1,4 +1,4 @@
-// sng_device_scope.h -- the one way the library selects a device (sng_api.cpp, sng_comm.cpp).
+// sng_device_scope.h -- the one way the library selects a device (sng_env.h's translation units, sng_comm.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,177 @@
+// sng_env.h -- the handle behind the C ABI (include/sng.h) and what the library's host translation units
+// share around it: sng_api.cpp (create, resets, steps, accessors), sng_state.cpp (checkpoints) and
+// sng_graph.cpp (day graphs, timed days, the bandwidth probe).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "sng.h"
+#include "sng_device_scope.h"
+#include "sng_host_tables.h"
+#include "sng_launch.h"
+#include "sng_layout.h"
+#include "sng_state_format.h"
+
+struct SngEnv {
+    SngConfig cfg{};
+    sng::Params p{};
+    sng::HostTables tables;
+    sng::Tables host_tab{};           // what d_tables holds
+    uint64_t cfg_hash = 0;            // configuration fingerprint (scalars + tables), checked by sng_set_state
+    std::vector<double> irradiance;   // owned copy
+    int device = 0;
+    int64_t E = 0;
+    uint64_t seed = 0;
+    int t = -1;                       // -1: never reset; T: day finished
+    bool day_finished = false;        // the reference's end-of-day Python draw (:181) is still owed
+    sng::DaySpans spans{0, 0, 0, sng::kSlots};   // 4 h, 10 h, 1 h in steps; per-charger array length of scenarios
+    // the day reset(generate_new_initial_values=False) replays: the last day sng_reset generated
+    // (the reference's initial_values.json, charging_station.py:185-186 / :119-136)
+    int gen_mode = -1;                // -1: none yet; else the SngRngMode that generated it
+    bool gen_loaded = false;          // its timeline is still the loaded one (no injected day since)
+    uint64_t replays = 0;             // device-RNG replays so far: the replay ratio stream's counter
+    sng::DeviceState ds{};
+    sng::Tables *d_tables = nullptr;
+    // host staging (pinned) for days built on the CPU
+    uint32_t *h_word = nullptr;
+    double *h_aux = nullptr, *h_req = nullptr, *h_ratio = nullptr, *h_pen0 = nullptr;
+    hipEvent_t staging_done = nullptr;
+    // reference RNG streams of every env (allocated on first use), both on the device: numpy's (rs, drawn by
+    // ref_day2_kernel) and Python's (ps below: two or three draws a day, seeded on host threads)
+    sng::RefStreams rs{};
+    bool np_seeded = false;
+    // the next day's stream blocks are prepared (mt_prepare_kernel) on a side stream while a day is stepped;
+    // every access to rs on a caller's stream first waits for prep_done
+    hipStream_t prep_stream = nullptr;
+    hipEvent_t prep_done = nullptr, day_drawn = nullptr;
+    bool prep_launched = false;   // prep_done marks a prepare launched on prep_stream
+
+    bool prepared = false;        // the next day's blocks are (being) prepared: no inline prepare
+    sng::RefStreams ps{};             // Python's `random` stream of every env, on the device (py_ratio_lane in observe0_kernel)
+    bool py_seeded = false;
+    // sng_step_host's I/O block: the step kernel reads its actions from and writes its outputs to host memory
+    // (mapped, coherent), so a host-driven step is one dispatch and one wait.  A/B (profiles/r06_single_env.log,
+    // SmartNanogridEnv.step at N = 10): 21.7 us per call against 25.4 us staged through a device block with a
+    // copy each way, and 34.2 us for round 5's torch copies; tools/io_latency.hip: 13.0 / 17.2 us in C
+    char *hio = nullptr, *hio_dev = nullptr;
+    size_t hio_bytes = 0;
+    std::string err;
+
+    size_t timeline() const { return (size_t)p.T * p.n * (size_t)E; }
+};
+
+struct SngGraph {
+    SngEnv *env = nullptr;
+    bool with_reset = false;
+    sng::DayKey key{};   // the loaded-day encoding the graph's steps were captured for
+    // the stream keys baked into the captured kernels' arguments: the device days a reset graph draws
+    // and the PV-ratio / profile streams are those of this seed and env offset
+    uint64_t seed = 0;
+    int64_t env_offset = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
+
+// Shared by the library's translation units, not exported by it.
+#pragma GCC visibility push(hidden)
+namespace sng {
+
+// The error text of a call without a handle (sng_create, the bandwidth probe), per thread; defined in sng_api.cpp.
+extern thread_local std::string g_create_error;
+
+inline int fail(SngEnv *env, int code, const std::string &msg) {
+    if (env) env->err = msg; else g_create_error = msg;
+    return code;
+}
+
+// The device generator keeps the day's vehicles of a charger plus an end sentinel in 8 LDS slots
+// (sng_kernels.hip, kDayVehicles): a vehicle stays >= 4/dt steps and leaves one step empty, so a
+// day has at most T / (4/dt + 1) + 1 vehicles, which must leave the sentinel's slot free.
+inline bool device_rng_ok(const SngEnv *env) { return env->spans.i4 >= 2 && env->p.T / (env->spans.i4 + 1) + 1 <= 7; }
+
+inline int hip_fail(SngEnv *env, hipError_t e, const char *what) {
+    return fail(env, SNG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(env, expr)                                   \
+    do {                                                     \
+        hipError_t _e = (expr);                              \
+        if (_e != hipSuccess) return hip_fail(env, _e, #expr); \
+    } while (0)
+// ... and of a helper that returns an SNG_* code and has set the handle's error itself
+#define SNG_TRY(expr)                     \
+    do {                                  \
+        if (int _rc = (expr)) return _rc; \
+    } while (0)
+
+// An entry point's prologue, after its argument checks: the rest of the call runs on the handle's device (DeviceScope).
+// A declaration and a statement that may return: once per function, at block scope, never under a brace-less `if`.
+#define ON_DEVICE_OF(env)               \
+    DeviceScope dev_((env)->device);    \
+    HIP_TRY(env, dev_.err)
+
+inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+
+// --- the loaded day (DayKey, t, day_finished, gen_mode, gen_loaded) ---
+inline void load_day(SngEnv *env, const DayKey &k) { env->p = with_day(env->p, k); }
+// a day begins: its t = 0 observation is queued
+inline void begin_day(SngEnv *env) {
+    env->t = 0;
+    env->day_finished = false;
+}
+// a generated day is now the one reset(generate_new_initial_values=False) replays
+inline void generated_day_loaded(SngEnv *env, int rng_mode) {
+    env->gen_mode = rng_mode;
+    env->gen_loaded = true;
+}
+// whole days ran (a day graph, the timed days): the last one is over
+inline void days_ran(SngEnv *env) {
+    env->t = env->p.T;
+    env->day_finished = true;
+}
+// A device day is counted by its first step (step_kernel advances the day counter); one that was reset but
+// never stepped is counted here, before what follows it, so the next device day drawn is a new one.
+inline hipError_t count_unstepped_device_day(SngEnv *env, hipStream_t st) {
+    return DayKey::of(env->p).unstepped_device_day(env->t) ? launch_bump_day(env->ds, st) : hipSuccess;
+}
+
+inline InfoPtrs info_ptrs(const SngInfo *i) {
+    InfoPtrs o{};
+    if (!i) return o;
+    o.grid_power = i->grid_power;
+    o.p_charge = i->total_charging_power;
+    o.p_discharge = i->total_discharging_power;
+    o.bess_soc = i->battery_state_of_charge;
+    o.pen_vehicle = i->total_vehicle_penalty;
+    o.pen_battery = i->total_battery_penalty;
+    o.grid_cost = i->grid_energy_cost;
+    o.total_cost = i->total_cost;
+    o.solar = i->utilized_solar_energy;
+    o.bess_power = i->battery_power_value;
+    o.bess_calc_power = i->battery_calculated_power;
+    o.nonexistent = i->nonexistent_vehicle_penalty;
+    o.bess_initial = i->initial_battery_soc;
+    o.flags = i->flags;
+    o.episode_return = i->episode_return;
+    o.charger_power = i->charger_power;
+    o.vehicle_soc = i->vehicle_soc;
+    o.flag_any = i->flag_summary;
+    return o;
+}
+
+inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
+
+// Defined in sng_api.cpp, called from sng_state.cpp and sng_graph.cpp too.
+// the requested-SoC plane, on first use
+int ensure_req(SngEnv *env);
+// Orders `st` after the side stream's preparation of the streams (sng_reset), before st touches them.
+int await_prepare(SngEnv *env, hipStream_t st);
+// one stream set's device blocks ([E][2][624] words and the positions), on first use
+int alloc_streams(SngEnv *env, RefStreams &r);
+// numpy's streams of every env, seeded on the device (mt_seed_kernel) if they are not yet, queued on `st`
+int ensure_np_streams(SngEnv *env, hipStream_t st);
+
+}  // namespace sng
+#pragma GCC visibility pop

@@ -1,0 +1,180 @@
+// sng_graph.cpp -- whole days in one call: days captured into a hipGraph (sng_graph_create / launch / destroy),
+// days timed kernel by kernel (sng_time_step_kernels), and the bandwidth probe bench.py's memory floor uses.
+#include <algorithm>
+
+#include "sng_env.h"
+
+using namespace sng;
+
+extern "C" {
+
+int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
+                     const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out) {
+    const bool with_reset = (flags & SNG_GRAPH_RESET) != 0;
+    if (!env || !actions || !obs || !reward || !done || !out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
+    if (days < 1 || (days > 1 && !with_reset))
+        return fail(env, SNG_ERR_INVALID_ARGUMENT, "days must be >= 1 (more than one needs SNG_GRAPH_RESET)");
+    if (with_reset && !device_rng_ok(env))
+        return fail(env, SNG_ERR_UNSUPPORTED, "device RNG needs time_interval <= 2h");
+    ON_DEVICE_OF(env);
+    if (env->p.req_enabled) SNG_TRY(ensure_req(env));
+    hipStream_t cs;
+    HIP_TRY(env, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    SngGraph *g = new SngGraph();
+    g->env = env;
+    // with a reset: every day a freshly generated device day (sng_reset(SNG_RNG_DEVICE)); else the loaded day
+    g->with_reset = with_reset;
+    g->key = with_reset ? DayKey::device_day(env->p) : DayKey::of(env->p);
+    const Params p = with_day(env->p, g->key);
+    g->seed = env->seed;
+    g->env_offset = p.env_offset;
+    const InfoPtrs ip = info_ptrs(info);
+    const DaySpans &sp = env->spans;
+    const int64_t E = env->E;
+    const int A = p.act_dim;
+    const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
+    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    for (int d = 0; e == hipSuccess && d < days; ++d) {
+        InfoPtrs ipd = ip;   // day d's returns into row d (observe0 zeroes it, every step adds)
+        if (day_returns) ipd.episode_return = day_returns + (size_t)d * E;
+        if (with_reset) {
+            e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs, ipd.episode_return, vec, cs);
+        }
+        for (int t = 0; e == hipSuccess && t < p.T; ++t)
+            e = launch_step(p, env->ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs, reward, done, E, t, vec, cs);
+    }
+    hipGraph_t graph = nullptr;
+    hipError_t e2 = hipStreamEndCapture(cs, &graph);
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
+    (void)hipStreamDestroy(cs);
+    if (e != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        delete g;
+        return hip_fail(env, e, "graph capture");
+    }
+    g->graph = graph;
+    *out = g;
+    return SNG_OK;
+}
+
+int sng_graph_launch(SngGraph *g, void *stream) {
+    if (!g) return SNG_ERR_INVALID_ARGUMENT;
+    SngEnv *env = g->env;
+    if (!g->with_reset) {
+        // a steps-only graph steps the loaded day from t = 0 with the Params it was captured with
+        if (!(g->key == DayKey::of(env->p)))
+            return fail(env, SNG_ERR_STATE,
+                        "graph captured for a day of another encoding (RNG mode, requested-SoC stream or replay): "
+                        "recapture it after this reset");
+        if (env->t != 0) return fail(env, SNG_ERR_STATE, "a steps-only graph starts at t = 0: reset first");
+    }
+    // sng_set_seed / sng_set_state / sng_set_env_offset since the capture: the graph's kernels would
+    // still draw the old streams
+    if (g->seed != env->seed || g->env_offset != env->p.env_offset)
+        return fail(env, SNG_ERR_STATE, "seed or env offset changed since the graph was captured: recapture it");
+    ON_DEVICE_OF(env);
+    // the graph's first reset must not redraw a device day that was reset but never stepped
+    if (g->with_reset) HIP_TRY(env, count_unstepped_device_day(env, as_stream(stream)));
+    HIP_TRY(env, hipGraphLaunch(g->exec, as_stream(stream)));
+    if (g->with_reset) {
+        load_day(env, g->key);
+        generated_day_loaded(env, SNG_RNG_DEVICE);
+    }
+    days_ran(env);
+    return SNG_OK;
+}
+
+void sng_graph_destroy(SngGraph *g) {
+    if (!g) return;
+    DeviceScope scope(g->env->device);
+    if (g->exec) (void)hipGraphExecDestroy(g->exec);
+    if (g->graph) (void)hipGraphDestroy(g->graph);
+    delete g;
+}
+
+int sng_time_step_kernels(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
+                          const SngInfo *info, int32_t days, float *ms, float *reset_ms, void *stream) {
+    if (!env || !actions || !obs || !reward || !done || days < 1)
+        return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
+    if (!device_rng_ok(env)) return fail(env, SNG_ERR_UNSUPPORTED, "device RNG needs time_interval <= 2h");
+    ON_DEVICE_OF(env);
+    hipStream_t st = as_stream(stream);
+    const DayKey key = DayKey::device_day(env->p);
+    const Params p = with_day(env->p, key);
+    if (p.req_stream) SNG_TRY(ensure_req(env));
+    const InfoPtrs ip = info_ptrs(info);
+    const DaySpans &sp = env->spans;
+    const int64_t E = env->E;
+    const int T = p.T, A = p.act_dim;
+    const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
+    std::vector<hipEvent_t> ev(ms ? 2 * (size_t)T * days : 0, nullptr), rev(reset_ms ? 2 * (size_t)days : 0, nullptr);
+    hipError_t e = count_unstepped_device_day(env, st);   // as in sng_reset
+    for (auto &x : ev)
+        if (e == hipSuccess) e = hipEventCreate(&x);
+    for (auto &x : rev)
+        if (e == hipSuccess) e = hipEventCreate(&x);
+    for (int d = 0; e == hipSuccess && d < days; ++d) {
+        e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs, ip.episode_return, vec, st,
+                            reset_ms ? rev[2 * (size_t)d] : nullptr, reset_ms ? rev[2 * (size_t)d + 1] : nullptr);
+        for (int t = 0; e == hipSuccess && t < T; ++t) {
+            hipEvent_t a = ms ? ev[2 * ((size_t)d * T + t)] : nullptr, b = ms ? ev[2 * ((size_t)d * T + t) + 1] : nullptr;
+            e = launch_step(p, env->ds, ip, env->host_tab, actions + (size_t)t * E * A, obs, reward, done, E, t, vec, st, a, b);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    for (int k = 0; e == hipSuccess && ms && k < T * days; ++k) e = hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]);
+    for (int d = 0; e == hipSuccess && reset_ms && d < days; ++d)
+        e = hipEventElapsedTime(&reset_ms[d], rev[2 * (size_t)d], rev[2 * (size_t)d + 1]);
+    for (auto x : ev)
+        if (x) (void)hipEventDestroy(x);
+    for (auto x : rev)
+        if (x) (void)hipEventDestroy(x);
+    if (e != hipSuccess) return hip_fail(env, e, "timed day");
+    load_day(env, key);
+    generated_day_loaded(env, SNG_RNG_DEVICE);
+    days_ran(env);
+    return SNG_OK;
+}
+
+int sng_bandwidth_probe(int device, int64_t read_bytes, int64_t write_bytes, int32_t reps, float *dispatch_us,
+                        float *back_to_back_us, void *stream) {
+    if (read_bytes < 0 || write_bytes < 0 || read_bytes + write_bytes < 16 || reps < 1)
+        return fail(nullptr, SNG_ERR_INVALID_ARGUMENT, "sng_bandwidth_probe: bad sizes");
+    DeviceScope scope(device);
+    if (scope.err != hipSuccess) return fail(nullptr, SNG_ERR_HIP, "sng_bandwidth_probe: hipSetDevice");
+    hipStream_t st = as_stream(stream);
+    const int64_t nr = read_bytes / 16, nw = write_bytes / 16;
+    void *in = nullptr, *out = nullptr;
+    std::vector<hipEvent_t> ev(2 * (size_t)reps + 2, nullptr);
+    hipError_t e = hipMalloc(&in, (size_t)std::max<int64_t>(nr, 1) * 16);
+    if (e == hipSuccess) e = hipMalloc(&out, (size_t)std::max<int64_t>(nw, 1) * 16);
+    if (e == hipSuccess) e = hipMemsetAsync(in, 0, (size_t)std::max<int64_t>(nr, 1) * 16, st);
+    for (auto &x : ev)
+        if (e == hipSuccess) e = hipEventCreate(&x);
+    // warm-up, then `reps` dispatches each between its own start/stop events (the dispatch's device time),
+    // then `reps` back to back between two events (start to start, as a graph runs kernels)
+    for (int k = 0; e == hipSuccess && k < 3; ++k) e = launch_probe_copy(in, out, nr, nw, st, nullptr, nullptr);
+    for (int k = 0; e == hipSuccess && k < reps; ++k)
+        e = launch_probe_copy(in, out, nr, nw, st, ev[2 * (size_t)k], ev[2 * (size_t)k + 1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[2 * (size_t)reps], st);
+    for (int k = 0; e == hipSuccess && k < reps; ++k) e = launch_probe_copy(in, out, nr, nw, st, nullptr, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev[2 * (size_t)reps + 1], st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    float sum = 0.f, ms = 0.f;
+    for (int k = 0; e == hipSuccess && k < reps; ++k) {
+        e = hipEventElapsedTime(&ms, ev[2 * (size_t)k], ev[2 * (size_t)k + 1]);
+        sum += ms;
+    }
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[2 * (size_t)reps], ev[2 * (size_t)reps + 1]);
+    for (auto x : ev)
+        if (x) (void)hipEventDestroy(x);
+    if (in) (void)hipFree(in);
+    if (out) (void)hipFree(out);
+    if (e != hipSuccess) return fail(nullptr, SNG_ERR_HIP, std::string("sng_bandwidth_probe: ") + hipGetErrorString(e));
+    if (dispatch_us) *dispatch_us = sum / reps * 1e3f;
+    if (back_to_back_us) *back_to_back_us = ms / reps * 1e3f;
+    return SNG_OK;
+}
+
+}  // extern "C"

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void probe_copy_kernel(const float4 *__restric
 }
 
 // ---------------------------------------------------------------------------------
-// launch wrappers (called from sng_api.cpp, declared in sng_launch.h)
+// launch wrappers (called from sng_api.cpp, sng_state.cpp and sng_graph.cpp, declared in sng_launch.h)
 // ---------------------------------------------------------------------------------
 // One launch, with optional start/stop events (both or neither): hipExtLaunchKernel stamps them with the
 // dispatch's own begin/end timestamps, i.e. the kernel's device time.
@@ -294,7 +294,7 @@ hipError_t launch_mt_prepare(const RefStreams &rs, int64_t E, hipStream_t stream
 
 // One reference-RNG day of every env into the word / aux (/ req) planes; ratio, pen0 and the t = 0
 // observation are the caller's (launch_observe0, which draws the Python streams).
-// prepare = false: the streams' blocks were prepared for this day already (sng_api.cpp prepares the next
+// prepare = false: the streams' blocks were prepared for this day already (sng_reset prepares the next
 // day's on a side stream while a day is stepped)
 hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStreams &rs, int64_t E, int i4, int i10,
                           int i1, bool prepare, hipStream_t stream) {

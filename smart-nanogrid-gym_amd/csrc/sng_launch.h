@@ -1,6 +1,6 @@
-// sng_launch.h -- what sng_api.cpp calls in sng_kernels.hip (the launch wrappers; the kernels they launch
-// live in the headers that file includes).  Both include it, so a changed signature is a
-// compile error in one of them; default arguments live here only.
+// sng_launch.h -- what the host translation units (through sng_env.h) call in sng_kernels.hip: the launch
+// wrappers; the kernels they launch live in the headers that file includes.  They all include it, so a changed
+// signature is a compile error in one of them; default arguments live here only.
 #pragma once
 #include <hip/hip_runtime.h>
 

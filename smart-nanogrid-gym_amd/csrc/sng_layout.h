@@ -171,7 +171,9 @@ SNG_HD inline uint32_t mt_untemper_word(uint32_t y) {
     y ^= y >> 18;                   // shifts of >= 16 bits undo in one step
     y ^= (y << 15) & 0xefc60000u;
     uint32_t t = y;                 // << 7: 5 steps cover 32 bits
+#ifdef __clang__   // g++, which compiles the host-only headers on their own, does not know the pragma
 #pragma unroll
+#endif
     for (int i = 0; i < 4; ++i) t = y ^ ((t << 7) & 0x9d2c5680u);
     y = t;
     t = y ^ (y >> 11);              // >> 11: 3 steps

@@ -13,7 +13,7 @@ namespace sng {
 // (np.random.seed(seed + global env), RandomState's state and draw semantics, sng_mt.h restates them
 // for the host) drives ChargingStation.generate_initial_vehicle_presence_per_charger
 // (charging_station.py:200-279) draw for draw, and the day is encoded into the word / f64 aux (/ req)
-// timeline exactly as the host encoder does it (sng_api.cpp encode_day).  Three kernels:
+// timeline exactly as the host encoder does it (sng_host_day.h encode_day).  Three kernels:
 //   mt_seed_kernel     init_genrand per env (once per seeding)
 //   mt_prepare_kernel  per env, one wavefront: the state one twist ahead into the other block (the
 //                      twist's three dependent ranges, 64 words at a time, in LDS)
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(kRefBlock) __attribute__((amdgpu_waves_per_eu(2))) 
             [[maybe_unused]] const unsigned long long t2_ = SNG_WNOW();
             const uint32_t *s_veh = list_veh(c % D);
             const double *s_soc = list_soc(c % D), *s_req = list_req(c % D);
-            // phase 2: the timeline (encode_day, sng_api.cpp): cur = the vehicle of step t until step t has
+            // phase 2: the timeline (encode_day, sng_host_day.h): cur = the vehicle of step t until step t has
             // passed its departure step, nxt the one after it (read a step ahead); a stay of zero steps
             // (dep == arrival, possible when 4/dt < 1) still marks its arrival step STATIC, as the host
             // encoder's arrival list does

@@ -1,28 +1,20 @@
-// Host-only stress check of sng_api.cpp's HostPool / parallel_ranges (the pool that draws the
+// Host-only stress check of sng_host_pool.h's HostPool / parallel_ranges_on (the pool that draws the
 // Python-stream PV ratios and seeds the streams): many parallel sections, every item visited exactly
-// once per section, no deadlock.  tests/test_host_pool.py extracts the pool's source text into
-// host_pool.inc and builds this file with g++ (with -fsanitize=thread when available).
-#include <algorithm>
+// once per section, no deadlock.  tests/test_host_pool.py builds this file with g++ against the header
+// (with -fsanitize=thread when available).
 #include <atomic>
-#include <condition_variable>
-#include <cstdint>
 #include <cstdio>
-#include <functional>
-#include <mutex>
-#include <thread>
-#include <vector>
-static int g_threads = 8;
-int host_threads() { return g_threads; }
-#include "host_pool.inc"
+
+#include "sng_host_pool.h"
+
 int main() {
     std::vector<long> v(100003, 0);
     int reps = 0;
     for (int t : {1, 2, 3, 8, 16}) {
-        g_threads = t;
         for (int rep = 0; rep < 300; ++rep, ++reps) {
             std::atomic<long> sum{0};
             const int64_t n = (int64_t)v.size() - rep;   // ragged sizes
-            parallel_ranges(n, 1024, [&](int64_t b, int64_t e) {
+            sng::parallel_ranges_on(t, n, 1024, [&](int64_t b, int64_t e) {
                 for (int64_t i = b; i < e; ++i) v[i] += 1;
                 sum += e - b;
             });

@@ -31,9 +31,9 @@ IDENT = re.compile(r"[A-Za-z_][A-Za-z0-9_]*")
 CONTENT_EXCEPTIONS = {
     ("include/sng.h", "charging_station.py", 50): "the penalty-mode switch reads the ctor's vehicle_uncharged_penalty_mode "
                                                   "through self.UNCHARGED_PENALTY_MODE",
-    ("smart-nanogrid-gym_amd/csrc/sng_api.cpp", "pv_system_manager.py", 17):
+    ("smart-nanogrid-gym_amd/csrc/sng_host_tables.h", "pv_system_manager.py", 17):
         "PVSystem(...)'s parameters at :17 give scaling_pv (the local of :68)",
-    ("smart-nanogrid-gym_amd/csrc/sng_api.cpp", "charging_station.py", 200):
+    ("smart-nanogrid-gym_amd/csrc/sng_host_day.h", "charging_station.py", 200):
         "the generator body; clear_initialisation_variables is cited separately (:138-150)",
     ("smart-nanogrid-gym_amd/csrc/sng_dev_env.h", "charging_station.py", 230):
         "the requested-SoC default 1.0 of the generator; the Requested_SOC key is the dict's",
