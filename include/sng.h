@@ -294,9 +294,16 @@ int sng_get_scenario(SngEnv *env, int64_t first, int64_t count, int32_t max_vehi
 int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_power, double *price,
                    double *price_max, int32_t *n);
 
-/* `days` full days captured as one hipGraph: ([device-RNG reset] + T fused steps) x days.
+/* `days` full days captured as one hipGraph: ([device-RNG reset] + the day's T steps) x days.
  * actions holds T consecutive [num_envs][act_dim] blocks (reused every day); obs/reward/done
  * are overwritten every step; info may be NULL.  Replays draw new days each time.
+ * Because every step's actions are known at capture and envs never interact, a day's T steps are one
+ * graph node where the step plan has a day kernel (packed device-RNG days of the wide family's stations:
+ * 10 chargers without V2X or stochastic profiles, and 50 chargers): each wavefront steps its envs through
+ * the whole day with SoC, BESS SoC and the day return in registers, and still stores every step's
+ * observation, reward, done and flags.  What is in memory after the graph has run is bit for bit what T
+ * step nodes leave; only the intermediate SoC / BESS SoC / day return of steps before the last are never
+ * written.  Every other plan, and SNG_GRAPH_STEP_NODES, captures T dependent step nodes.
  * flags: SNG_GRAPH_*; days > 1 needs SNG_GRAPH_RESET.
  * day_returns (device [days][num_envs] f64, may be NULL): day d's returns accumulate into row
  * d instead of info->episode_return, so a replay leaves every day's returns for one
@@ -306,10 +313,13 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
  * packed records, requested-SoC stream, cleared Requested_SOC, day-counter ownership), so launching a
  * steps-only graph over a day of another encoding than at capture, or after t = 0, fails with
  * SNG_ERR_STATE. */
-#define SNG_GRAPH_RESET 1   /* start every day with a device-RNG reset */
+#define SNG_GRAPH_RESET 1        /* start every day with a device-RNG reset */
+#define SNG_GRAPH_STEP_NODES 2   /* one graph node per step even where a day kernel exists (A/B, tests) */
 int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                      const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out);
 int sng_graph_launch(SngGraph *graph, void *stream);
+/* Graph nodes that step one day: 1 with the day kernel, else T (-1 for NULL). */
+int sng_graph_step_nodes(const SngGraph *graph);
 /* Kernel-time probe: runs `days` device-RNG days eagerly (as the graph does) and returns the
  * device time (ms) of every step kernel, ms[days*T], from HIP start/stop events attached to
  * each dispatch (hipExtLaunchKernel: the dispatch's own begin/end timestamps), and, when reset_ms

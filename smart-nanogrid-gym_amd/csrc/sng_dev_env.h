@@ -65,14 +65,20 @@ __device__ __forceinline__ double profile_factor(uint64_t env_seed, uint32_t dom
     return profile_factor_key(stream_key(env_seed, 0, domain, day), k, sigma);
 }
 // The day's profile keys of an env (PV, price) from DeviceState::prof_key ([E][2] u32, one 8 B load).
-__device__ __forceinline__ void profile_factors(const Params &p, const DeviceState &s, uint32_t el8, int t,
-                                                double *fpv, double *fpr) {
-    const v2u kk = __builtin_bit_cast(v2u, bld(reinterpret_cast<const uint64_t *>(s.prof_key), el8));
+__device__ __forceinline__ v2u profile_keys(const DeviceState &s, uint32_t el8) {
+    return __builtin_bit_cast(v2u, bld(reinterpret_cast<const uint64_t *>(s.prof_key), el8));
+}
+// The factors of t..t+3 from the day's keys (the day kernel loads the keys once a day).
+__device__ __forceinline__ void expand_profile_factors(const Params &p, v2u kk, int t, double *fpv, double *fpr) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         fpv[j] = profile_factor_key(kk.x, t + j, p.pv_noise);
         fpr[j] = profile_factor_key(kk.y, t + j, p.price_noise);
     }
+}
+__device__ __forceinline__ void profile_factors(const Params &p, const DeviceState &s, uint32_t el8, int t,
+                                                double *fpv, double *fpr) {
+    expand_profile_factors(p, profile_keys(s, el8), t, fpv, fpr);
 }
 
 // Per-step constants staged in LDS by the step kernel: irr_norm[t..t+3], price_norm[t..t+3],
@@ -190,12 +196,15 @@ __device__ __forceinline__ ChargerResult charger_step(const Params &p, uint32_t 
 // penaliser.py:104-111): the new SoC (stored), its penalty and powers, and what it adds to the grid
 // balance.  It needs only the BESS SoC and action, not the chargers, so the wide step kernel runs it
 // before the charger loop (while the chargers' loads are in flight); env_tail runs it in place otherwise.
+// STORE = false (the day kernel): the new SoC stays with the caller (BessStep::bess), who stores it after the
+// day's last step; the day's initial SoC (bess0, t = 0) is stored either way.
 // ---------------------------------------------------------------------------------
 struct BessStep {
     double bess, pen_b, bpow, bcalc, pw, dp;
     bool moved, chg;
     uint32_t fl;
 };
+template <bool STORE = true>
 __device__ __forceinline__ BessStep bess_step(const Params &p, const DeviceState &s, uint32_t el8, int t, double bess,
                                               float bess_action) {
     BessStep b{bess, 0.0, 0.0, 0.0, 0.0, 0.0, false, false, 0u};
@@ -227,24 +236,25 @@ __device__ __forceinline__ BessStep bess_step(const Params &p, const DeviceState
     } else if (!(b.bess <= 1.0)) {
         b.fl |= SNG_FLAG_BESS_SOC_ABOVE_1;
     }
-    bst<kNT>(s.bess, el8, b.bess);
+    if constexpr (STORE) bst<kNT>(s.bess, el8, b.bess);
     return b;
 }
 
 // ---------------------------------------------------------------------------------
 // Env tail: BESS (unless PRE: bess_step ran before the chargers), grid energy, cost, reward
 // (central_management_system.py:99-185, penaliser.py:177-187, accountant.py:26-40) and the observation's
-// BESS entry.  Leader lane only.
+// BESS entry.  Leader lane only.  KEEP (the day kernel, with PRE): the day return so far goes to *ret_keep instead
+// of memory.
 // ---------------------------------------------------------------------------------
 static_assert((SNG_FLAG_NEGATIVE_DEMAND | SNG_FLAG_CHARGING_MODE | SNG_FLAG_BESS_SOC_ABOVE_1 | SNG_FLAG_V2X_BREAKPOINT) == 0xfu,
               "env_tail ORs the flag summary bit by bit: bits 0-3");
-template <bool DIAG, bool PRE = false>
+template <bool DIAG, bool PRE = false, bool KEEP = false>
 __device__ __forceinline__ void env_tail(const Params &p, const DeviceState &s, const InfoPtrs &info, int64_t e0, uint32_t lo, uint32_t el1, uint32_t el8,
                                          int t, double ratio, double bess, float bess_action, double p_ch,
                                          double p_dis, double pen_v, double nonexist, uint32_t fl, float *o_row,
                                          const double *cst, const double *fpv, const double *fpr, double ret_prev,
                                          double bess0, double *__restrict__ reward, uint8_t *__restrict__ done,
-                                         const BessStep *pre = nullptr) {
+                                         const BessStep *pre = nullptr, double *ret_keep = nullptr) {
     // no global loads in here: a load would wait (vmcnt) for every SoC store the env just issued
     const double solar = p.pv ? (cst[CST_PV] * ratio) * fpv[0] : 0.0;   // central_management_system.py:99-103
     const double demand = p_ch + p_dis;                            // :105
@@ -287,7 +297,8 @@ __device__ __forceinline__ void env_tail(const Params &p, const DeviceState &s, 
             atomicOr(info.flag_any + ((uint32_t)(e0 >> 5) & (SNG_FLAG_SUMMARY_WORDS - 1)), any);
     }
     if (info.flags) bst(info.flags, el1 * 4u, fl);
-    if (info.episode_return) bst<kNT>(info.episode_return, el8, ret_prev + -total);
+    if constexpr (KEEP) *ret_keep = ret_prev + -total;
+    else if (info.episode_return) bst<kNT>(info.episode_return, el8, ret_prev + -total);
     if (DIAG) {
         if (info.grid_power) bst(info.grid_power, el8, (double)(grid));
         if (info.p_charge) bst(info.p_charge, el8, (double)(p_ch));

@@ -227,4 +227,14 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Global memory ordering inside one wavefront: some lanes' stores before other lanes' loads of the same
+// addresses.  A wavefront's vector memory operations go through one L1 in issue order; the workgroup-scope
+// fences (a workgroup is one wavefront wherever this is used) also wait for the stores, which the rare paths
+// that use it can afford.
+__device__ __forceinline__ void wave_mem_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 }  // namespace sng

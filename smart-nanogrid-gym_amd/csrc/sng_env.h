@@ -65,6 +65,7 @@ struct SngEnv {
 struct SngGraph {
     SngEnv *env = nullptr;
     bool with_reset = false;
+    bool day_kernel = false;   // each day's steps are one day-kernel node (sng_step_day.h), not T step nodes
     sng::DayKey key{};   // the loaded-day encoding the graph's steps were captured for
     // the stream keys baked into the captured kernels' arguments: the device days a reset graph draws
     // and the PV-ratio / profile streams are those of this seed and env offset

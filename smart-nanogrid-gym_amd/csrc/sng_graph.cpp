@@ -33,12 +33,19 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     const int64_t E = env->E;
     const int A = p.act_dim;
     const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
+    // a day's T steps as one day-kernel node where the plan has one (the wide family's packed days), else --
+    // or with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
+    g->day_kernel = !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip) != 0;
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     for (int d = 0; e == hipSuccess && d < days; ++d) {
         InfoPtrs ipd = ip;   // day d's returns into row d (observe0 zeroes it, every step adds)
         if (day_returns) ipd.episode_return = day_returns + (size_t)d * E;
         if (with_reset) {
             e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs, ipd.episode_return, vec, cs);
+        }
+        if (g->day_kernel) {
+            if (e == hipSuccess) e = launch_day(p, env->ds, ipd, actions, obs, reward, done, E, 0, p.T, vec, cs);
+            continue;
         }
         for (int t = 0; e == hipSuccess && t < p.T; ++t)
             e = launch_step(p, env->ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs, reward, done, E, t, vec, cs);
@@ -83,6 +90,11 @@ int sng_graph_launch(SngGraph *g, void *stream) {
     }
     days_ran(env);
     return SNG_OK;
+}
+
+int sng_graph_step_nodes(const SngGraph *g) {
+    if (!g) return -1;
+    return g->day_kernel ? 1 : g->env->p.T;
 }
 
 void sng_graph_destroy(SngGraph *g) {

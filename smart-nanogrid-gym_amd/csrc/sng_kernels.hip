@@ -36,6 +36,7 @@
 #include "sng_dev_env.h"        // one env's step arithmetic: charger, BESS, env tail
 #include "sng_step_lean.h"      // step_lean_kernel
 #include "sng_step_wide.h"      // step_wide_kernel
+#include "sng_step_day.h"       // day_wide_kernel
 #include "sng_step_general.h"   // step_kernel
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
 
@@ -191,6 +192,37 @@ hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &in
     for (int i = 0; i < CST_COUNT; ++i) k.v[i] = step_constant(&tab, t, i);
     return launch_kernel(l.by_const, l.grid, l.block, l.lds, stream, ev_start, ev_stop, act, obs, reward, done, E, t,
                          vec_io, k, p, s, info);
+}
+
+// The day kernel of a plan: the packed days of the wide family's 10-charger station (sng_step_day.h); every other
+// plan has none.  N = 50 is not compiled: with every charger's SoC kept next to the step's 239 VGPRs it spills
+// (325-423 VGPR spills, 0.8-1 KB of scratch), so config 5's days stay T step nodes.
+typedef void (*DayKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, Params, DeviceState,
+                          InfoPtrs);
+template <int NC>
+static StepLaunch day_launch(const StepPlan &pl, int64_t E, DayKernel &kern) {
+    constexpr int L = kWideLanes;
+    static constexpr DayKernel k[2][2] = {{day_wide_kernel<NC, L, false, false>, day_wide_kernel<NC, L, false, true>},
+                                          {day_wide_kernel<NC, L, true, false>, day_wide_kernel<NC, L, true, true>}};
+    using Lay = WideLds<NC, L>;
+    kern = k[pl.req][pl.noise];
+    return {nullptr, nullptr, blocks_for(E, Lay::WENVS), dim3(kWave), Lay::BYTES};
+}
+
+int day_kernel_available(const Params &p, const InfoPtrs &info) {
+    const StepPlan pl = step_plan(p, info_diag(info));
+    return (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10) ? 1 : 0;
+}
+
+hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
+                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream) {
+    if (!day_kernel_available(p, info)) return hipErrorNotSupported;
+    if (t0 < 0 || nt < 1 || t0 + nt > p.T) return hipErrorInvalidValue;
+    const StepPlan pl = step_plan(p, info_diag(info));
+    DayKernel kern = nullptr;
+    const StepLaunch l = day_launch<10>(pl, E, kern);
+    return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
+                         vec_io, p, s, info);
 }
 
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len) {

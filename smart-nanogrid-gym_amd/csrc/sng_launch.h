@@ -12,6 +12,12 @@ namespace sng {
 hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
                        hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// Steps t0 .. t0 + nt - 1 of the loaded day in one launch (sng_step_day.h); `act` is step t0's block of nt
+// consecutive [E][act_dim] blocks.  hipErrorNotSupported for a plan without a day kernel
+// (day_kernel_available == 0): the caller launches the steps one by one.
+int day_kernel_available(const Params &p, const InfoPtrs &info);
+hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
+                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream);
 hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
                            int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
                            int py = 0);

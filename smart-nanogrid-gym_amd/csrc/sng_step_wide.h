@@ -102,10 +102,8 @@ struct WideGroup {
         if constexpr (kPairs) return j < H ? row4 : row4_last;
         return ragged(j) ? (j < nc ? row4 + (uint32_t)j * (uint32_t)E * 4u : row4_last) : row4;
     }
-    // loads oldest-needed-first: the actions tile and the per-env values, then every charger's state
-    __device__ __forceinline__ void issue(int64_t e0_, const float *act, int64_t E, int t, int vec_io, const Params &p,
-                                          const DeviceState &s, const InfoPtrs &info, int lane) {
-        SNG_WSTAMP(0);
+    // the lane's env and its byte offsets: the same for every step of a day
+    __device__ __forceinline__ void place(int64_t e0_, int64_t E, int lane) {
         const int le = lane / L, part = lane % L;
         e0 = e0_;
         nw = (E - e0) < WENVS ? (int)(E - e0) : WENVS;
@@ -114,8 +112,7 @@ struct WideGroup {
         el1 = (uint32_t)el;
         el4 = el1 * 4u;
         el8 = el1 * 8u;
-        const int c0 = part * CPL;
-        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
+        [[maybe_unused]] const int c0 = part * CPL;
         if constexpr (kPairs) {
             row4 = el4 + (uint32_t)(part * H) * (uint32_t)E * 4u;     // charger part H + j, j < H: + j E (uniform)
             row4_last = el4 + (uint32_t)part * (uint32_t)E * 4u;      // charger N - 2 + part: + (N - 2) E (uniform)
@@ -130,42 +127,95 @@ struct WideGroup {
             row4 = el4 + (uint32_t)c0 * (uint32_t)E * 4u;
             row4_last = el4 + (uint32_t)(NC - 1) * (uint32_t)E * 4u;
         }
-        const size_t plane = (size_t)t * NC * (size_t)E;   // this step's timeline planes
-        const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1
-        const int Ad = p.act_dim;
-        act_tile.issue(act + e0 * Ad, nw * Ad, vec_io != 0, lane);
-        ratio = bld(s.ratio, el8);
-        bess_l = bld(p.bess ? s.bess : s.ratio, el8);
+    }
+    // charger j of the lane: its SoC load -- a pair's 16 B with the pair's second charger, the last pair's 8 B
+    __device__ __forceinline__ void issue_soc(int j, int lane, int64_t E, const DeviceState &s) {
+        if constexpr (kPairs) {
+            if (j < H && (j & 1)) bld2(s.soc, soc_a, (uint32_t)(j - 1) * (uint32_t)E * 8u, run_[j - 1], run_[j]);
+            if (j == H) run_[j] = bld(s.soc, soc_b, (uint32_t)(NC - 2) * (uint32_t)E * 8u);
+        } else {
+            const int c0 = (lane % L) * CPL;
+            const int c = c0 + j < NC ? c0 + j : NC - 1;
+            run_[j] = bld(s.soc, (uint32_t)soc_index(c, (int64_t)el1, NC, E) * 8u);
+        }
+    }
+    // ... and its SoC store, with the same pairing (v: the lane's chargers' values)
+    __device__ __forceinline__ void store_soc(int j, int lane, int64_t E, const DeviceState &s, const double *v) {
+        if constexpr (kPairs) {
+            if (j < H && (j & 1)) bst2<kNT>(s.soc, soc_a, v[j - 1], v[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
+            if (j == H) bst<kNT>(s.soc, soc_b, v[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
+        } else {
+            const int c = charger(lane % L, j);
+            if (c < NC) bst<kNT>(s.soc, (uint32_t)soc_index(c, el1, NC, E) * 8u, v[j]);   // a ragged lane's range ends
+        }
+    }
+    // the day kernel's state back to memory: every charger's SoC (a live lane's own chargers), and after the
+    // day's last step the BESS SoC and the day return too
+    __device__ __forceinline__ void store_state_soc(int64_t E, const DeviceState &s, int lane) {
+        if (live) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) fpv[j] = fpr[j] = 1.0;
-        if constexpr (NOISE) profile_factors(p, s, el8, t, fpv, fpr);   // the day's profile factors of t..t+3
+            for (int j = 0; j < CPL; ++j) store_soc(j, lane, E, s, run_);
+        }
+    }
+    __device__ __forceinline__ void store_state(int64_t E, const Params &p, const DeviceState &s, const InfoPtrs &info,
+                                                int lane) {
+        store_state_soc(E, s, lane);
+        if (live && lane % L == 0) {
+            if (p.bess) bst<kNT>(s.bess, el8, bess_l);
+            if (info.episode_return) bst<kNT>(info.episode_return, el8, ret_l);
+        }
+    }
+    // loads oldest-needed-first: the actions tile and the per-env values, then every charger's state.
+    // STEP: what one step reads (its actions tile, records, requested SoC and profile factors); STATE: what
+    // passes from step to step (PV ratio, BESS SoC, the t = 0 penalty, the day return and every charger's
+    // SoC).  step_wide_kernel issues both, interleaved as below; the day kernel (sng_step_day.h) issues the
+    // state once a day and each step's inputs with issue_step_inputs.
+    template <bool STATE = true, bool STEP = true>
+    __device__ __forceinline__ void issue(int64_t e0_, const float *act, int64_t E, int t, int vec_io, const Params &p,
+                                          const DeviceState &s, const InfoPtrs &info, int lane) {
+        SNG_WSTAMP(0);
+        place(e0_, E, lane);
+        const int part = lane % L;
+        const int c0 = part * CPL;
+        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
+        [[maybe_unused]] const size_t plane = (size_t)t * NC * (size_t)E;   // this step's timeline planes
+        [[maybe_unused]] const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1
+        [[maybe_unused]] const int Ad = p.act_dim;
+        if constexpr (STEP) act_tile.issue(act + e0 * Ad, nw * Ad, vec_io != 0, lane);
+        if constexpr (STATE) {
+            ratio = bld(s.ratio, el8);
+            bess_l = bld(p.bess ? s.bess : s.ratio, el8);
+        }
+        if constexpr (STEP) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fpv[j] = fpr[j] = 1.0;
+            if constexpr (NOISE) profile_factors(p, s, el8, t, fpv, fpr);   // the day's profile factors of t..t+3
+        }
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             // charger `charger(part, j)` (past a ragged lane's range: its charger NC - 1 again, discarded)
             const uint32_t v4 = row_of(j, nc, E), r4 = r4_of(j, E), v8 = 2u * v4, r8 = 2u * r4;
-            if (PK) {   // 2 B records in charger quads: the lane's whole quads as 8 B, its last-pair charger as 2 B
-                if constexpr (kQuads) {
-                    if (j < H && (j & 3) == 0)
-                        unpack_quad(bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)j * (uint32_t)E * 2u),
-                                    w + j);
-                    if (j == H) w[j] = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
+            if constexpr (STEP) {
+                if (PK) {   // 2 B records in charger quads: the lane's whole quads as 8 B, its last-pair charger as 2 B
+                    if constexpr (kQuads) {
+                        if (j < H && (j & 3) == 0)
+                            unpack_quad(bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)j * (uint32_t)E * 2u),
+                                        w + j);
+                        if (j == H) w[j] = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
+                    } else {
+                        const int cr = charger(part, j) < NC ? charger(part, j) : NC - 1;
+                        const RecOff ro = rec_off(cr, NC, E, el1);
+                        w[j] = bld16(rec_t, ro.v, ro.s);
+                    }
                 } else {
-                    const int cr = charger(part, j) < NC ? charger(part, j) : NC - 1;
-                    const RecOff ro = rec_off(cr, NC, E, el1);
-                    w[j] = bld16(rec_t, ro.v, ro.s);
+                    w[j] = bld(s.word + plane, v4, r4);
+                    aux[PK ? 0 : j] = bld(s.aux + plane, v8, r8);
                 }
-            } else {
-                w[j] = bld(s.word + plane, v4, r4);
-                aux[PK ? 0 : j] = bld(s.aux + plane, v8, r8);
             }
-            if constexpr (kPairs) {   // a pair's 16 B once both its records are issued; the last pair's 8 B
-                if (j < H && (j & 1)) bld2(s.soc, soc_a, (uint32_t)(j - 1) * (uint32_t)E * 8u, run_[j - 1], run_[j]);
-                if (j == H) run_[j] = bld(s.soc, soc_b, (uint32_t)(NC - 2) * (uint32_t)E * 8u);
-            } else {
-                const int c = c0 + j < NC ? c0 + j : NC - 1;
-                run_[j] = bld(s.soc, (uint32_t)soc_index(c, el, NC, E) * 8u);
-            }
-            if (REQ) req[REQ ? j : 0] = bld(s.req + plane, v8, r8);
+            // a pair's 16 B once both its records are issued; the last pair's 8 B
+            if constexpr (STATE) issue_soc(j, lane, E, s);
+            if constexpr (STEP)
+                if (REQ) req[REQ ? j : 0] = bld(s.req + plane, v8, r8);
         }
         // the t = 0 penalty and the day return are read only by the env tail: issued behind every charger's
         // loads, so the waits before the chargers (the header's PV ratio, the BESS step's SoC) do not count them
@@ -173,15 +223,56 @@ struct WideGroup {
         // Stores issued earlier or in bursts measured slower there: the observation tile stored before the env
         // tail +0.33 us, its copy-out unrolled (every LDS read, then every 16 B store) +0.6 us, the SoC pairs
         // stored after the charger loop +0.3 us -- paced stores leave the other wavefronts' loads alone.
-        pen0_l = bld(t == 0 ? s.pen0 : s.ratio, el8);
-        ret_l = bld(info.episode_return ? info.episode_return : s.ratio, el8);
+        if constexpr (STATE) {
+            pen0_l = bld(t == 0 ? s.pen0 : s.ratio, el8);
+            ret_l = bld(info.episode_return ? info.episode_return : s.ratio, el8);
+        }
+    }
+    // One step's inputs of a packed day, for the day kernel: the actions tile into act_tile, the step's records
+    // as they lie in memory (the lane's quads and its last-pair record: rq, rl; take_step_inputs unpacks them
+    // into w[] once the step before has read its own), the requested SoC, and the step's table constants
+    // (uniform loads through s.tables: a per-launch StepConst cannot carry T steps).
+    static constexpr int NQ = kQuads ? H / 4 : 1;
+    uint64_t rq[NQ];
+    uint32_t rl;
+    double reqn[REQ ? CPL : 1];
+    StepConst kn;
+    __device__ __forceinline__ void issue_step_inputs(const float *act, int64_t E, int t, int vec_io, const Params &p,
+                                                      const DeviceState &s, int lane) {
+        static_assert(PK && kQuads, "the day kernel steps packed days of stations whose lanes own whole record quads");
+        const size_t plane = (size_t)t * NC * (size_t)E;
+        const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1, as issue()
+#pragma unroll
+        for (int i = 0; i < CST_COUNT; ++i) kn.v[i] = step_constant(s.tables, t, i);
+        act_tile.issue(act + e0 * p.act_dim, nw * p.act_dim, vec_io != 0, lane);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            rq[q] = bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)(4 * q) * (uint32_t)E * 2u);
+        rl = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
+        if constexpr (REQ) {
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) reqn[j] = bld(s.req + plane, 2u * row_of(j, CPL, E), 2u * r4_of(j, E));
+        }
+    }
+    __device__ __forceinline__ void take_step_inputs() {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) unpack_quad(rq[q], w + 4 * q);
+        w[H] = rl;
+        if constexpr (REQ) {
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) req[j] = reqn[j];
+        }
     }
     // the requested SoC at python index t-1 of charger j of the lane, or its default without the stream
     __device__ __forceinline__ double req_of(int j, const Params &p) const {
         return REQ ? req[REQ ? j : 0] : req_default(p);
     }
 
-    // the group's step; s_act holds its actions tile (committed), s_obs is the wavefront's observation tile
+    // the group's step; s_act holds its actions tile (committed), s_obs is the wavefront's observation tile.
+    // KEEP (the day kernel): what the next step of the same env would load straight back stays in registers --
+    // every charger's new SoC in run_[], the BESS SoC in bess_l, the day return in ret_l -- and the caller
+    // stores it after the day's last step (store_state); every other output is stored as always.
+    template <bool KEEP = false>
     __device__ __forceinline__ void run(const float *s_act, float *s_obs, float *obs, double *reward, uint8_t *done,
                                         int64_t E, int t, int vec_io, const StepConst &k, const Params &p,
                                         const DeviceState &s, const InfoPtrs &info, int lane) {
@@ -214,7 +305,7 @@ struct WideGroup {
         BessStep bs{};
         if (live && leader) {
             write_obs_header(o_row, p, k.v + CST_IRR, k.v + CST_PN, ratio, fpv, fpr);
-            bs = bess_step(p, s, el8, t, p.bess ? bess_l : 0.0, bess_action);
+            bs = bess_step<!KEEP>(p, s, el8, t, p.bess ? bess_l : 0.0, bess_action);
             if (p.bess) o_row[O - 1] = (float)bs.bess;
         }
 
@@ -240,7 +331,9 @@ struct WideGroup {
                                                                            PK ? 0.0 : aux[PK ? 0 : j], run_[j], req_of(j, p),
                                                                            av[j], t, recip_cap((double)capi));
                     sv[j] = (PK && !occ) ? (double)rec_soc(w[j]) : r.soc;
-                    if constexpr (kPairs) {   // a pair's 16 B once both its chargers are stepped; the last pair's 8 B
+                    if constexpr (KEEP) {
+                        run_[j] = sv[j];
+                    } else if constexpr (kPairs) {   // a pair's 16 B once both its chargers are stepped; the last pair's 8 B
                         if (j < H && (j & 1))
                             bst2<kNT>(s.soc, soc_a, sv[j - 1], sv[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
                         if (j == H) bst<kNT>(s.soc, soc_b, sv[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
@@ -328,6 +421,13 @@ struct WideGroup {
             PairwiseSum pos, neg;
             pos.init();
             neg.init();
+            // KEEP: this path keeps memory as its SoC state (the first lane steps the other lanes' chargers
+            // too), so the wavefront's SoC registers go to memory before it and come back after it; the
+            // wavefront's own stores and loads of an address stay in order (one L1 for the whole wavefront)
+            if constexpr (KEEP) {
+                store_state_soc(E, s, lane);
+                wave_mem_fence();
+            }
             if (live && leader) {
 #pragma unroll 1
                 for (int c = 0; c < NC; ++c) {
@@ -354,13 +454,19 @@ struct WideGroup {
             }
             p_ch = pos.result();
             p_dis = neg.result();
+            if constexpr (KEEP) {
+                wave_mem_fence();
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) issue_soc(j, lane, E, s);
+            }
         }
         SNG_WSTAMP(2);
         if (live && leader) {
             pen_v += (t == 0) ? pen0_l : 0.0;   // python index -1 slot; every per-charger term is 0 at t = 0
-            env_tail<false, true>(p, s, info, e0, (uint32_t)le, el1, el8, t, ratio, p.bess ? bess_l : 0.0, bess_action,
-                                  p_ch, p_dis, pen_v, 100.0 * (double)n_nonexist, fl, o_row, k.v, fpv, fpr,
-                                  info.episode_return ? ret_l : 0.0, 0.0, reward, done, &bs);
+            env_tail<false, true, KEEP>(p, s, info, e0, (uint32_t)le, el1, el8, t, ratio, p.bess ? bess_l : 0.0,
+                                        bess_action, p_ch, p_dis, pen_v, 100.0 * (double)n_nonexist, fl, o_row, k.v, fpv,
+                                        fpr, info.episode_return ? ret_l : 0.0, 0.0, reward, done, &bs, &ret_l);
+            if constexpr (KEEP) bess_l = bs.bess;
         }
         SNG_WSTAMP(3);
         wave_lds_fence();

@@ -22,6 +22,8 @@ ABI_VERSION = 10
 SNG_OK = 0
 RNG_REFERENCE = 0
 RNG_DEVICE = 1
+GRAPH_RESET = 1        # sng.h SNG_GRAPH_RESET
+GRAPH_STEP_NODES = 2   # sng.h SNG_GRAPH_STEP_NODES
 FLAG_NEGATIVE_DEMAND = 0x1
 FLAG_CHARGING_MODE = 0x2
 FLAG_BESS_SOC_ABOVE_1 = 0x4
@@ -136,6 +138,7 @@ EXPORTS = {
                                         ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int, ctypes.c_int32,
                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "sng_graph_launch": (ctypes.c_int, [ctypes.c_void_p, _S]),
+    "sng_graph_step_nodes": (ctypes.c_int, [ctypes.c_void_p]),
     "sng_graph_destroy": (None, [ctypes.c_void_p]),
     "sng_time_step_kernels": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int32, c_float_p,
@@ -172,7 +175,12 @@ def lib():
                 "or `make -C smart-nanogrid-gym_amd/csrc` (there is no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in EXPORTS.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # additions to the ABI (sng_graph_step_nodes) keep its version: an older build lacks the symbol
+                raise NativeLibraryMissing(f"{LIB_PATH} does not export {name}: it is an older build of the "
+                                           "library, rebuild it (make -C smart-nanogrid-gym_amd/csrc)") from None
             fn.restype = res
             fn.argtypes = args
         if L.sng_abi_version() != ABI_VERSION:

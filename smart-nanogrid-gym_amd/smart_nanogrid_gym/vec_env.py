@@ -916,9 +916,11 @@ class SmartNanogridVecEnv(_VecEnvBase):
 
 class EpisodeGraph:
     """Whole days (device-RNG reset + T fused steps, x days) captured once as a hipGraph and
-    replayed; actions come from a device tensor [T, E, act_dim] reused every day."""
+    replayed; actions come from a device tensor [T, E, act_dim] reused every day.  Where the station has a day
+    kernel (include/sng.h, sng_graph_create) a day's T steps are one graph node; step_nodes=True keeps one
+    node per step (the same results; for A/B and tests)."""
 
-    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None):
+    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False):
         """days > 1 captures that many consecutive days (each with its reset) in one graph,
         which amortises the graph launch.  day_returns: optional device tensor [days, E] f64;
         day d's returns accumulate into row d (instead of venv.return_d).  A seed left by seed() takes effect
@@ -944,8 +946,15 @@ class EpisodeGraph:
                                          ctypes.c_void_p(venv.obs_d.data_ptr()),
                                          ctypes.c_void_p(venv.reward_d.data_ptr()),
                                          ctypes.c_void_p(venv.done_d.data_ptr()), ctypes.byref(venv._info),
-                                         int(with_reset), self.days, dr, ctypes.byref(g)), venv._h)
+                                         (_native.GRAPH_RESET if with_reset else 0)
+                                         | (_native.GRAPH_STEP_NODES if step_nodes else 0),
+                                         self.days, dr, ctypes.byref(g)), venv._h)
         self._g = g
+
+    @property
+    def step_nodes_per_day(self):
+        """Graph nodes that step one day: 1 with the day kernel, else T."""
+        return int(lib().sng_graph_step_nodes(self._g))
 
     def launch(self, stream=None):
         s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)

@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""A/B of the two forms a captured day can take (include/sng.h, sng_graph_create): one day-kernel node per day
+against T step nodes (SNG_GRAPH_STEP_NODES), in one process, on one box, interleaved.
+
+  tools/day_kernel_ab.py [--envs E] [--chargers N] [--time-interval 15min --extended-day --pv-noise s --price-noise s]
+                         [--days 100] [--graph-days 20] [--warmup 8] [--rounds 3]
+
+The env, the actions and the graph shape are bench.py's (device-RNG days, `graph-days` days per replay, the day
+return accumulated, no per-env flag array).  Each round replays the step-node graph for `days` days, then the
+default graph, each between HIP events on the graphs' stream after `warmup` days of its own; one JSON line per
+round with the device time per day of both forms, then one summary line.  With SNG_LIBRARY pointing at another
+build of this source (say one compiled with day_prefetch() returning false) it measures that build the same way.
+A station without a day kernel reports the same form twice (step_nodes_per_day says so)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "smart-nanogrid-gym_amd"))
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--chargers", type=int, default=10)
+    ap.add_argument("--time-interval", default="1h")
+    ap.add_argument("--extended-day", action="store_true")
+    ap.add_argument("--pv-noise", type=float, default=0.0)
+    ap.add_argument("--price-noise", type=float, default=0.0)
+    ap.add_argument("--days", type=int, default=100)
+    ap.add_argument("--graph-days", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=2024)
+    args = ap.parse_args()
+    from smart_nanogrid_gym import EpisodeGraph, SmartNanogridVecEnv
+    from smart_nanogrid_gym._native import lib
+
+    kw = dict(number_of_chargers=args.chargers, time_interval=args.time_interval, charging_mode="bounded",
+              vehicle_uncharged_penalty_mode="sparse", pv_system_available_in_model=True,
+              battery_system_available_in_model=True)
+    if args.extended_day or args.pv_noise > 0 or args.price_noise > 0:
+        kw.update(extended_day=args.extended_day, pv_noise=args.pv_noise, price_noise=args.price_noise)
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    E = args.envs
+    venv = SmartNanogridVecEnv(E, seed=args.seed, device=0, rng="device", **kw)
+    T, A = venv.timesteps, venv.act_dim
+    g = torch.Generator(device=device).manual_seed(args.seed)
+    low = torch.tensor(venv.action_space.low, device=device)
+    high = torch.tensor(venv.action_space.high, device=device)
+    acts = low + (high - low) * torch.rand((T, E, A), generator=g, device=device)
+    acts = torch.where(torch.rand(acts.shape, generator=g, device=device) < 0.2, torch.zeros_like(acts), acts)
+    acts = acts.contiguous()
+    venv._info.flags = None   # as bench.py without --per-env-flags
+    venv.reset_tensors(rng="device")
+    D = max(1, args.graph_days)
+    while args.days % D:
+        D -= 1
+    forms = {"step_nodes": EpisodeGraph(venv, acts, days=D, step_nodes=True), "default": EpisodeGraph(venv, acts, days=D)}
+    nodes = {k: v.step_nodes_per_day for k, v in forms.items()}
+
+    def timed(graph):
+        for _ in range(-(-args.warmup // D)):
+            graph.launch()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.days // D):
+            graph.launch()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.days
+
+    rows = []
+    for r in range(args.rounds):
+        row = {k: round(timed(v), 3) for k, v in forms.items()}
+        rows.append(row)
+        print(json.dumps({"round": r, "day_gpu_us": row}), flush=True)
+    best = {k: min(r[k] for r in rows) for k in forms}
+    print(json.dumps({"build_id": lib().sng_build_id().decode(), "library": os.environ.get("SNG_LIBRARY", "in-tree"),
+                      "envs": E, "chargers": args.chargers, "T": T, "graph_days": D, "step_nodes_per_day": nodes,
+                      "day_gpu_us_min": best, "env_steps_per_s_min_time": {k: round(E * T / (v * 1e-6)) for k, v in best.items()},
+                      "ratio_step_nodes_over_default": round(best["step_nodes"] / best["default"], 4)}), flush=True)
+    for v in forms.values():
+        v.close()
+    venv.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

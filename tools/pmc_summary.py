@@ -5,7 +5,8 @@
 Reads <out>/prof/run_kernel_stats.csv (--kernel-trace --stats) and the two PMC passes
 <out>/pmc_fetch/run_counter_collection.csv (FETCH_SIZE) and <out>/pmc_write/... (WRITE_SIZE),
 writes profiles/<tag>_kernel_stats.csv, profiles/<tag>_pmc.csv and an entry of
-profiles/pmc_step_kernel.json; the same for config 5 from prof_cfg5/, pmc5_fetch/ and pmc5_write/
+profiles/pmc_step_kernel.json (or profiles/pmc_day_kernel.json for a run whose graphs hold one day_wide_kernel node
+per day: a launch is then a whole day); the same for config 5 from prof_cfg5/, pmc5_fetch/ and pmc5_write/
 (profiles/<tag>_kernel_stats_config5.csv, profiles/<tag>_pmc_config5.csv).  Every entry carries the build id of
 the library measured (<out>/build_id.txt, written by tools/gpu_session.sh; sng_build_id()), and the rocprof
 summaries are listed with theirs in profiles/kernel_stats_index.json: bench.py --full quotes only measurements of the
@@ -51,6 +52,11 @@ def main():
         entries = entries if isinstance(entries, list) else [entries]
     except (OSError, ValueError):
         entries = []
+    day_path = os.path.join(prof, "pmc_day_kernel.json")
+    try:
+        day_entries = json.load(open(day_path))
+    except (OSError, ValueError):
+        day_entries = []
     # (pass prefix, file suffix, envs, chargers): the headline workload and config 5
     for pre, suf, envs, chargers in (("", "", 65536, 10), ("pmc5_", "_config5", 65536, 50)):
         stats = os.path.join(out, "prof" + ("_cfg5" if suf else ""), "run_kernel_stats.csv")
@@ -76,16 +82,23 @@ def main():
             wr = csv.DictWriter(fp, fieldnames=list(rows[0]))
             wr.writeheader()
             wr.writerows(rows)
-        step = [r for r in rows if "step_" in r["kernel"]][0]
-        meta = dict(source=f"profiles/{tag}_pmc{suf}.csv (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes)",
-                    build_id=build_id, kernel=step["kernel"], envs=envs, chargers=chargers, bytes_per_launch=step["hbm_bytes_per_launch"],
-                    fetch_kib=step["fetch_kib"], write_kib=step["write_kib"],
-                    correction="traffic = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE counts half of streamed reads)")
-        entries = [e for e in entries if not (e.get("envs") == envs and e.get("chargers") == chargers
-                                              and e.get("build_id") == build_id)] + [meta]
+        # the kernel that steps the graph's days: the step kernel (pmc_step_kernel.json, one step per launch, which
+        # bench.py --full and tests/test_bench_model_cpu.py hold against the step's byte model), and where the
+        # graph has one node per day the day kernel (pmc_day_kernel.json: bytes_per_launch is a whole day's)
+        for kind, into in (("step_", entries), ("day_wide_kernel", day_entries)):
+            for step in [r for r in rows if kind in r["kernel"]][:1]:
+                meta = dict(source=f"profiles/{tag}_pmc{suf}.csv (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes)",
+                            build_id=build_id, kernel=step["kernel"], envs=envs, chargers=chargers,
+                            bytes_per_launch=step["hbm_bytes_per_launch"],
+                            fetch_kib=step["fetch_kib"], write_kib=step["write_kib"],
+                            correction="traffic = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE counts half of streamed reads)")
+                into[:] = [e for e in into if not (e.get("envs") == envs and e.get("chargers") == chargers
+                                                   and e.get("build_id") == build_id)] + [meta]
         for r in rows:
             print(r)
     json.dump(entries, open(meta_path, "w"), indent=1)
+    if day_entries:
+        json.dump(day_entries, open(day_path, "w"), indent=1)
     json.dump(index, open(idx_path, "w"), indent=1)
 
 
