@@ -111,6 +111,15 @@ __device__ __forceinline__ double div_by_cap(double x, double c, double r) {
     return __builtin_fma(__builtin_fma(-q, c, x), r, q);
 }
 
+// 1/c for an integer capacity c in [1, 255]: v_rcp_f64 and one Newton step.  div_by_cap needs only a
+// relative error far below 2^-31 here (its quotient then errs by < 2^-62 relative before the last
+// rounding, which x/c's distance from a rounding midpoint, >= 2^-62, absorbs): v_rcp_f64's error
+// squared by the Newton step is ~2^-46.  c = 0 (empty charger) gives NaN, which charger_step selects away.
+__device__ __forceinline__ double recip_cap(double c) {
+    const double r0 = __builtin_amdgcn_rcp(c);
+    return __builtin_fma(r0, __builtin_fma(-c, r0, 1.0), r0);
+}
+
 // ---------------------------------------------------------------------------------
 // One charger, one step: penalty term of the vehicle present at t-1 and the EV update.
 // penalise_charging_vehicles_outside_bounds (penaliser.py:39-57, 71-87): SoC and requested
@@ -136,7 +145,7 @@ struct ChargerResult {
 // branch -- the inverted-flag power (charger.py:122-132) and max(0, calc) -- is never selected and is not
 // computed; every value this returns equals the general form's for such actions.
 // PK: w is a device-RNG day's packed record (its capacity in bits 3-9), else a word.
-template <bool FAST, bool RCP, bool NONNEG = false, bool PK = false>
+template <bool FAST, bool NONNEG = false, bool PK = false>
 __device__ __forceinline__ ChargerResult charger_step(const Params &p, uint32_t w, double aux, double run, double req,
                                                       float a, int t, double rcap) {
     ChargerResult o;
@@ -161,9 +170,8 @@ __device__ __forceinline__ ChargerResult charger_step(const Params &p, uint32_t 
         const float pf = __fmul_rn(__fmul_rn(a, p.ev_power_f), p.ev_eff_f);
         const float pdt = __fmul_rn(pf, p.dt_f);
         pc = (double)pf;
-        // RCP: exact reciprocal-fma division with r ~ 1/c (the LDS table, or recip_cap); otherwise
-        // the division itself -- all are the IEEE quotient
-        change = RCP ? div_by_cap((double)pdt, cap, rcap) : (double)pdt / cap;
+        // exact reciprocal-fma division with rcap ~ 1/c (the LDS table, or recip_cap): the IEEE quotient
+        change = div_by_cap((double)pdt, cap, rcap);
     }
     const double calc = prev + change;
     if constexpr (NONNEG) {   // a > 0 charges, a == 0 idles (chg == !idle)
@@ -189,6 +197,39 @@ __device__ __forceinline__ ChargerResult charger_step(const Params &p, uint32_t 
     o.nx = (!occ && !idle) ? 1u : 0u;
     o.fl = (occ && !idle && !p.bounded) ? (uint32_t)SNG_FLAG_CHARGING_MODE : 0u;
     return o;
+}
+
+// ---------------------------------------------------------------------------------
+// One charger's visit by a step kernel: charger_step on the charger's record as the kernel loaded it, and what
+// every kernel then writes for that charger.  What a packed (device-RNG) day's record means is said here and
+// nowhere else (sng_layout.h has the format):
+//   - an arriving vehicle's SoC is the running SoC the step before stored (the record it carried), so the step
+//     sees no STATIC bit and no aux plane (aux is not read);
+//   - an empty charger's SoC state is the record's own SoC field, and its departure entry is that of a record
+//     without steps left.
+// The caller stores `soc` where and how its layout has it, writes the two observation entries, and keeps the
+// sums of r.pw, r.q, r.nx and r.fl in its own order.  1 / capacity is recip_cap's, or with TABLE the entry of
+// the caller's table by capacity (the general kernel stages one in LDS for N <= 16); both are exact (div_by_cap).
+// ---------------------------------------------------------------------------------
+template <bool PK>
+struct ChargerVisit {
+    ChargerResult r;
+    double soc;       // the charger's SoC state after the step
+    uint32_t w_dep;   // the record whose steps-left field the observation shows
+    // the charger's observation entries: SOC[c, t] and the time to departure / 24
+    __device__ __forceinline__ float obs_soc() const { return (float)r.soc; }
+    __device__ __forceinline__ float obs_dep() const { return departure_obs<PK>(w_dep); }
+};
+template <bool FAST, bool NONNEG, bool PK, bool TABLE = false>
+__device__ __forceinline__ ChargerVisit<PK> visit_charger(const Params &p, uint32_t w, const double &aux, double run,
+                                                          double req, float a, int t, const double *rcp_table = nullptr) {
+    const uint32_t capi = cap_field<PK>(w);
+    const bool occ = (w & W_OCC) != 0;
+    ChargerVisit<PK> v{charger_step<FAST, NONNEG, PK>(p, PK ? (w & ~W_STATIC) : w, PK ? 0.0 : aux, run, req, a, t,
+                                                      TABLE ? rcp_table[capi] : recip_cap((double)capi)),
+                       0.0, (PK && !occ) ? 0u : w};
+    v.soc = (PK && !occ) ? (double)rec_soc(w) : v.r.soc;
+    return v;
 }
 
 // ---------------------------------------------------------------------------------
@@ -314,15 +355,6 @@ __device__ __forceinline__ void env_tail(const Params &p, const DeviceState &s, 
         if (info.nonexistent) bst(info.nonexistent, el8, (double)(nonexist));
         if (info.bess_initial) bst(info.bess_initial, el8, (double)(p.bess ? bess0 : 0.0));
     }
-}
-
-// 1/c for an integer capacity c in [1, 255]: v_rcp_f64 and one Newton step.  div_by_cap needs only a
-// relative error far below 2^-31 here (its quotient then errs by < 2^-62 relative before the last
-// rounding, which x/c's distance from a rounding midpoint, >= 2^-62, absorbs): v_rcp_f64's error
-// squared by the Newton step is ~2^-46.  c = 0 (empty charger) gives NaN, which charger_step selects away.
-__device__ __forceinline__ double recip_cap(double c) {
-    const double r0 = __builtin_amdgcn_rcp(c);
-    return __builtin_fma(r0, __builtin_fma(-c, r0, 1.0), r0);
 }
 
 // This step's table constants by value: a kernel argument of the lean and the wide step kernel (launch_step

@@ -24,8 +24,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "sng.h"
 #include "sng_launch.h"
 #include "sng_layout.h"

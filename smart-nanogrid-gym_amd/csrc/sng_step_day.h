@@ -9,12 +9,10 @@
 
 namespace sng {
 
-// Whether step t + 1's loads (its actions tile, records, requested SoC and table constants) are issued before
-// step t's first store or after its last.  A store counts in vmcnt ahead of every later load, so a load issued
-// behind step t's stores waits for them; issued ahead of them it costs registers for the whole step (the raw
-// records, the tile's registers and, with the stream, the requested SoC).
-constexpr bool day_prefetch(int nc) { return nc <= 16; }
-
+// Step t + 1's loads (its actions tile, records, requested SoC and table constants) are issued before step t's
+// first store.  A store counts in vmcnt ahead of every later load, so a load issued behind step t's stores waits
+// for them; issued ahead of them it costs registers for the whole step (the raw records, the tile's registers
+// and, with the stream, the requested SoC).
 // Geometry as step_wide_kernel's: one wavefront per workgroup, WideLds<NC, L>::WENVS envs per wavefront, the
 // same LDS tiles.  `act` is step t0's [E][act_dim] block, the later steps' blocks follow it.
 //   once a day:  the PV ratio, BESS SoC, t = 0 penalty, day return, profile keys and every charger's SoC are
@@ -33,7 +31,6 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
                 InfoPtrs info) {
     using Grp = WideGroup<NC, L, true, REQ, NOISE>;
     using Lay = WideLds<NC, L>;
-    constexpr bool PF = day_prefetch(NC);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     float *s_obs = lds + Lay::ACT;   // the actions tile, then the observation tile
@@ -54,11 +51,9 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
         g.act_tile.commit(lds, lane);
         wave_lds_fence();
         if constexpr (NOISE) expand_profile_factors(p, keys, t, g.fpv, g.fpr);
-        const bool more = t + 1 < t1;
-        const float *next = act + (size_t)(t + 1 - t0) * block;
-        if (PF && more) g.issue_step_inputs(next, E, t + 1, vec_io, p, s, lane);   // ahead of this step's stores
+        if (t + 1 < t1)   // ahead of this step's stores
+            g.issue_step_inputs(act + (size_t)(t + 1 - t0) * block, E, t + 1, vec_io, p, s, lane);
         g.template run<true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
-        if (!PF && more) g.issue_step_inputs(next, E, t + 1, vec_io, p, s, lane);
         wave_lds_fence();   // the next step's tile writes stay behind this step's reads of both tiles
     }
     g.store_state(E, p, s, info, lane);

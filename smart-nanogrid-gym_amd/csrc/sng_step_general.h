@@ -283,7 +283,6 @@ __global__ __launch_bounds__(step_block(NC)) __attribute__((amdgpu_waves_per_eu(
             }
             // the batch's actions ahead of the LDS writes below (they issue back to back)
             float av[CH];
-            double rc[CH];
 #pragma unroll
             for (int j = 0; j < CH; ++j) {
                 const int c = c0 + j;
@@ -297,20 +296,17 @@ __global__ __launch_bounds__(step_block(NC)) __attribute__((amdgpu_waves_per_eu(
                 // 1/cap from the LDS table here, not ahead with the actions: it needs charger j's
                 // record, and reading every record's up front waited for all of them
                 // (wide stations: recip_cap instead of the LDS table, exact all the same -- div_by_cap)
-                rc[j] = kRows ? s_rcp[cap_field<PK>(w[j])] : recip_cap((double)cap_field<PK>(w[j]));
-                // a packed day: the arrival SoC is the running SoC the step before stored (sng_layout.h)
-                const bool occ = (w[j] & W_OCC) != 0;
-                const uint32_t wj = PK ? (w[j] & ~W_STATIC) : w[j];
-                const double aux_j = PK ? 0.0 : aux[j];
-                const ChargerResult r = charger_step<FAST, true, false, PK>(p, wj, aux_j, run[j], req[j], av[j], t, rc[j]);
+                const ChargerVisit<PK> v =
+                    visit_charger<FAST, false, PK, kRows>(p, w[j], aux[j], run[j], req[j], av[j], t, s_rcp);
+                const ChargerResult &r = v.r;
                 const SocOff so = soc_off(c, n, E, el8);
-                bst<kNT>(socv, so.v, (PK && !occ) ? (double)rec_soc(w[j]) : r.soc, so.s);
+                bst<kNT>(socv, so.v, v.soc, so.s);
                 if (DIAG) {   // 'Charger power values' and the SOC[c, t] the day record holds
                     if (info.charger_power) info.charger_power[(size_t)e * n + c] = r.pw;
                     if (info.vehicle_soc) info.vehicle_soc[(size_t)e * n + c] = r.soc;
                 }
-                o_row[k_soc + c] = (float)r.soc;
-                o_row[k_soc + n + c] = departure_obs<PK>((PK && !occ) ? 0u : w[j]);
+                o_row[k_soc + c] = v.obs_soc();
+                o_row[k_soc + n + c] = v.obs_dep();
                 n_nonexist += r.nx;
                 fl |= r.fl;
                 if (L == 1) {
@@ -386,7 +382,7 @@ __global__ __launch_bounds__(step_block(NC)) __attribute__((amdgpu_waves_per_eu(
     // a device-RNG day's first step advances the day counter its reset read (generate_kernel);
     // nothing in this launch reads it (done last: at the top it perturbed the prologue's schedule).
     // A replayed day (bump_day = 0) drew no counter value of its own.
-    if (PK && t == 0 && p.bump_day && blockIdx.x == 0 && threadIdx.x == 0) *s.episode += 1;
+    bump_day_counter<PK>(p, s, t);
 }
 
 }  // namespace sng

@@ -132,19 +132,15 @@ __global__ __launch_bounds__(kLeanBlock) void step_lean_kernel(const float *__re
     if (live) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const uint32_t capi = cap_field<PK>(w[c]);
-            // a packed day: an arriving vehicle's SoC is the running SoC the step before stored (the
-            // record it carried), so the step sees no STATIC bit and an empty charger's SoC is 0
-            const bool occ = (w[c] & W_OCC) != 0;
-            const ChargerResult r = charger_step<true, true, false, PK>(p, PK ? (w[c] & ~W_STATIC) : w[c], PK ? 0.0 : aux[c],
-                                                                        run[c], req[c], av[c], t, recip_cap((double)capi));
-            sv[c] = (PK && !occ) ? (double)rec_soc(w[c]) : r.soc;
+            const ChargerVisit<PK> v = visit_charger<true, false, PK>(p, w[c], aux[c], run[c], req[c], av[c], t);
+            const ChargerResult &r = v.r;
+            sv[c] = v.soc;
             if (c & 1)   // the pair's 16 B slot once both chargers are stepped
                 bst2<kNT>(s.soc, 2u * el8, sv[c - 1], sv[c], (uint32_t)(c - 1) * (uint32_t)E * 8u);
             else if (c == NC - 1)
                 bst<kNT>(s.soc, el8, sv[c], (uint32_t)c * (uint32_t)E * 8u);
-            o_row[k_soc + c] = (float)r.soc;
-            o_row[k_soc + NC + c] = departure_obs<PK>((PK && !occ) ? 0u : w[c]);
+            o_row[k_soc + c] = v.obs_soc();
+            o_row[k_soc + NC + c] = v.obs_dep();
             n_nonexist += r.nx;
             fl |= r.fl;
             pen_v += r.q;

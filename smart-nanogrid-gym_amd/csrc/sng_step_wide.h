@@ -1,6 +1,6 @@
-// sng_step_wide.h -- the wide lean step kernel (step_wide_kernel): L lanes per env, every charger's state in
-// registers; the headline station (N = 10, two lanes) and config 5 (N = 50).
-// Needs <type_traits>, sng_dev_util.h (buffer access, TileStage, copy_out, wave_lds_fence), sng_dev_sums.h
+// sng_step_wide.h -- the wide lean step kernel (step_wide_kernel): two lanes per env, every charger's state in
+// registers; the headline station (N = 10) and config 5 (N = 50).
+// Needs sng_dev_util.h (buffer access, TileStage, copy_out, wave_lds_fence), sng_dev_sums.h
 // (PairwiseSum) and sng_dev_env.h (charger_step, bess_step, env_tail, StepConst, ...).  Included by
 // sng_kernels.hip only.
 #pragma once
@@ -37,33 +37,32 @@ struct WideLds {
     static constexpr size_t BYTES = (size_t)(ACT + OBS) * 4;
 };
 
-// Lane `part` K's value of an env's L adjacent lanes (L = 2 or 4), for the env's first lane, by DPP quad
-// permutation (the env's lanes never straddle a quad).
-template <int L, int K>
+// Lane `part` K's value of an env's two adjacent lanes, for the env's first lane, by DPP quad permutation (a
+// quad holds two envs: lanes 0-1 and 2-3).
+template <int K>
 __device__ __forceinline__ uint32_t from_part(uint32_t x) {
-    constexpr int ctrl = L == 2 ? (K | (K << 2) | ((K + 2) << 4) | ((K + 2) << 6)) : (K | (K << 2) | (K << 4) | (K << 6));
+    constexpr int ctrl = K | (K << 2) | ((K + 2) << 4) | ((K + 2) << 6);
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, ctrl, 0xF, 0xF, false);
 }
-template <int L, int K>
+template <int K>
 __device__ __forceinline__ double from_part(double x) {
     const uint64_t b = __builtin_bit_cast(uint64_t, x);
-    const uint64_t lo = from_part<L, K>((uint32_t)b), hi = from_part<L, K>((uint32_t)(b >> 32));
+    const uint64_t lo = from_part<K>((uint32_t)b), hi = from_part<K>((uint32_t)(b >> 32));
     return __builtin_bit_cast(double, lo | (hi << 32));
 }
 
-// The WENVS = 64 / L envs of a wavefront: their loads (issue), then their step (run).  step_wide_kernel, below,
-// says how the L lanes of an env share its chargers.
+// The WENVS = 32 envs of a wavefront: their loads (issue), then their step (run).  step_wide_kernel, below,
+// says how the two lanes of an env share its chargers.
 template <int NC, int L, bool PK, bool REQ, bool NOISE>
 struct WideGroup {
     using Lay = WideLds<NC, L>;
-    static constexpr int WENVS = Lay::WENVS, CPL = (NC + L - 1) / L;
+    // The one supported shape: two lanes per env and N = 2 mod 8 (the headline's 10, config 5's 50).  Lane
+    // `part` steps the chargers [part H, part H + H) (H = (N - 2) / 2, a multiple of 4) and charger
+    // N - 2 + part of the last pair, so its SoC state moves as whole 16 B charger pairs and its records as whole
+    // 8 B quads (sng_layout.h) but for that last charger: 8 B of the last pair, 2 B of the partial quad.
+    static_assert(L == 2 && NC % 8 == 2, "two lanes per env, each with whole charger pairs and record quads");
+    static constexpr int WENVS = Lay::WENVS, H = (NC - 2) / 2, CPL = H + 1;
     static constexpr int KT = (Lay::A * WENVS + 4 * kWave - 1) / (4 * kWave);
-    static_assert((L - 1) * CPL < NC, "every lane steps at least one charger");
-    // The lane's chargers.  Two lanes and N = 2 mod 4 (the headline's 10, config 5's 50): lane `part` steps the
-    // whole charger pairs [part H, part H + H) (H = (N - 2) / 2) and charger N - 2 + part of the last pair, so
-    // its SoC state moves as 16 B charger pairs (sng_layout.h) but for that last charger.  Otherwise the
-    // contiguous ranges [part CPL, min(N, part CPL + CPL)).
-    static constexpr bool kPairs = L == 2 && NC % 4 == 2;
     // the fast loop's charger step without the discharge branch (charger_step NONNEG) for the headline's
     // station (step 6.60-6.66 -> 6.53-6.56 us, profiles/r04_ab_nonneg.txt).  At N = 50 the compiler merges
     // several chargers' select masks ahead of the per-charger scheduling barriers and spills them (332
@@ -71,14 +70,7 @@ struct WideGroup {
     // config 5 ran 22.62-22.69 against 22.47-22.54 us (profiles/r04_ab_config5_nonneg.txt): its step is
     // bound by its bytes, so config 5 keeps the general form
     static constexpr bool kNonneg = NC <= 16;
-    static constexpr int H = (NC - 2) / 2;
-    static_assert(!kPairs || CPL == H + 1, "a lane's chargers: H from whole pairs and one from the last");
-    // the lane's whole pairs are whole record quads too (H a multiple of 4: N = 10, 50), and the last pair is
-    // the partial quad's two records
-    static constexpr bool kQuads = kPairs && H % 4 == 0;
-    static __device__ __forceinline__ int charger(int part, int j) {
-        return kPairs ? (j < H ? part * H + j : NC - 2 + part) : part * CPL + j;
-    }
+    static __device__ __forceinline__ int charger(int part, int j) { return j < H ? part * H + j : NC - 2 + part; }
     int64_t e0;
     int nw;
     bool live;
@@ -90,18 +82,12 @@ struct WideGroup {
     double aux[PK ? 1 : CPL], run_[CPL], req[REQ ? CPL : 1];
     SNG_WSTAMP_DECL;   // diagnostic builds: 0 issue, 1 actions tile staged, 2 chargers, 3 env tail, 4 obs stores issued
 
-    // the (per-lane, uniform) byte offsets of charger j of the lane in a [N][E] u32 plane: j * E in the uniform
-    // part, except for the j some lane lacks (a ragged last lane) or the last pair's charger, where the
-    // per-lane part carries it
-    static __device__ __forceinline__ bool ragged(int j) { return !kPairs && NC % L != 0 && j >= NC - (L - 1) * CPL; }
-    __device__ __forceinline__ uint32_t r4_of(int j, int64_t E) const {
-        if constexpr (kPairs) return (uint32_t)(j < H ? j : NC - 2) * (uint32_t)E * 4u;
-        return ragged(j) ? 0u : (uint32_t)j * (uint32_t)E * 4u;
+    // the (per-lane, uniform) byte offsets of charger j of the lane in a [N][E] u32 plane: the lane's first row
+    // (or its last-pair charger's) in the per-lane part, j * E (or (N - 2) * E) in the uniform part
+    static __device__ __forceinline__ uint32_t r4_of(int j, int64_t E) {
+        return (uint32_t)(j < H ? j : NC - 2) * (uint32_t)E * 4u;
     }
-    __device__ __forceinline__ uint32_t row_of(int j, int nc, int64_t E) const {
-        if constexpr (kPairs) return j < H ? row4 : row4_last;
-        return ragged(j) ? (j < nc ? row4 + (uint32_t)j * (uint32_t)E * 4u : row4_last) : row4;
-    }
+    __device__ __forceinline__ uint32_t row_of(int j) const { return j < H ? row4 : row4_last; }
     // the lane's env and its byte offsets: the same for every step of a day
     __device__ __forceinline__ void place(int64_t e0_, int64_t E, int lane) {
         const int le = lane / L, part = lane % L;
@@ -112,54 +98,35 @@ struct WideGroup {
         el1 = (uint32_t)el;
         el4 = el1 * 4u;
         el8 = el1 * 8u;
-        [[maybe_unused]] const int c0 = part * CPL;
-        if constexpr (kPairs) {
-            row4 = el4 + (uint32_t)(part * H) * (uint32_t)E * 4u;     // charger part H + j, j < H: + j E (uniform)
-            row4_last = el4 + (uint32_t)part * (uint32_t)E * 4u;      // charger N - 2 + part: + (N - 2) E (uniform)
-            soc_a = 2u * el8 + (uint32_t)(part * H) * (uint32_t)E * 8u;   // pair row part H + j: + j E 8 (uniform)
-            soc_b = 2u * el8 + (uint32_t)part * 8u;                      // the last pair's row: + (N - 2) E 8
-            rec_a = el1 * 8u + (uint32_t)(part * H) * (uint32_t)E * 2u;   // quad row part H + j: + j E 2 (uniform)
-            rec_b = el1 * 4u + (uint32_t)part * 2u;                      // the partial quad (N - 2, N - 1): + (N - 2) E 2
-        } else {
-            // the lane's first charger row as a per-lane byte offset; charger j of the lane adds j * E
-            // (uniform).  Past the lane's range (j >= nc) the loads re-read its first charger and nothing is
-            // stored.
-            row4 = el4 + (uint32_t)c0 * (uint32_t)E * 4u;
-            row4_last = el4 + (uint32_t)(NC - 1) * (uint32_t)E * 4u;
-        }
+        row4 = el4 + (uint32_t)(part * H) * (uint32_t)E * 4u;     // charger part H + j, j < H: + j E (uniform)
+        row4_last = el4 + (uint32_t)part * (uint32_t)E * 4u;      // charger N - 2 + part: + (N - 2) E (uniform)
+        soc_a = 2u * el8 + (uint32_t)(part * H) * (uint32_t)E * 8u;   // pair row part H + j: + j E 8 (uniform)
+        soc_b = 2u * el8 + (uint32_t)part * 8u;                      // the last pair's row: + (N - 2) E 8
+        rec_a = el1 * 8u + (uint32_t)(part * H) * (uint32_t)E * 2u;   // quad row part H + j: + j E 2 (uniform)
+        rec_b = el1 * 4u + (uint32_t)part * 2u;                      // the partial quad (N - 2, N - 1): + (N - 2) E 2
     }
     // charger j of the lane: its SoC load -- a pair's 16 B with the pair's second charger, the last pair's 8 B
-    __device__ __forceinline__ void issue_soc(int j, int lane, int64_t E, const DeviceState &s) {
-        if constexpr (kPairs) {
-            if (j < H && (j & 1)) bld2(s.soc, soc_a, (uint32_t)(j - 1) * (uint32_t)E * 8u, run_[j - 1], run_[j]);
-            if (j == H) run_[j] = bld(s.soc, soc_b, (uint32_t)(NC - 2) * (uint32_t)E * 8u);
-        } else {
-            const int c0 = (lane % L) * CPL;
-            const int c = c0 + j < NC ? c0 + j : NC - 1;
-            run_[j] = bld(s.soc, (uint32_t)soc_index(c, (int64_t)el1, NC, E) * 8u);
-        }
+    __device__ __forceinline__ void issue_soc(int j, int64_t E, const DeviceState &s) {
+        if (j < H && (j & 1)) bld2(s.soc, soc_a, (uint32_t)(j - 1) * (uint32_t)E * 8u, run_[j - 1], run_[j]);
+        if (j == H) run_[j] = bld(s.soc, soc_b, (uint32_t)(NC - 2) * (uint32_t)E * 8u);
     }
-    // ... and its SoC store, with the same pairing (v: the lane's chargers' values)
-    __device__ __forceinline__ void store_soc(int j, int lane, int64_t E, const DeviceState &s, const double *v) {
-        if constexpr (kPairs) {
-            if (j < H && (j & 1)) bst2<kNT>(s.soc, soc_a, v[j - 1], v[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
-            if (j == H) bst<kNT>(s.soc, soc_b, v[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
-        } else {
-            const int c = charger(lane % L, j);
-            if (c < NC) bst<kNT>(s.soc, (uint32_t)soc_index(c, el1, NC, E) * 8u, v[j]);   // a ragged lane's range ends
-        }
+    // ... and its SoC store, with the same pairing (v: the lane's chargers' values): a pair's 16 B once both its
+    // chargers are stepped, the last pair's 8 B
+    __device__ __forceinline__ void store_soc(int j, int64_t E, const DeviceState &s, const double *v) {
+        if (j < H && (j & 1)) bst2<kNT>(s.soc, soc_a, v[j - 1], v[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
+        if (j == H) bst<kNT>(s.soc, soc_b, v[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
     }
     // the day kernel's state back to memory: every charger's SoC (a live lane's own chargers), and after the
     // day's last step the BESS SoC and the day return too
-    __device__ __forceinline__ void store_state_soc(int64_t E, const DeviceState &s, int lane) {
+    __device__ __forceinline__ void store_state_soc(int64_t E, const DeviceState &s) {
         if (live) {
 #pragma unroll
-            for (int j = 0; j < CPL; ++j) store_soc(j, lane, E, s, run_);
+            for (int j = 0; j < CPL; ++j) store_soc(j, E, s, run_);
         }
     }
     __device__ __forceinline__ void store_state(int64_t E, const Params &p, const DeviceState &s, const InfoPtrs &info,
                                                 int lane) {
-        store_state_soc(E, s, lane);
+        store_state_soc(E, s);
         if (live && lane % L == 0) {
             if (p.bess) bst<kNT>(s.bess, el8, bess_l);
             if (info.episode_return) bst<kNT>(info.episode_return, el8, ret_l);
@@ -175,9 +142,6 @@ struct WideGroup {
                                           const DeviceState &s, const InfoPtrs &info, int lane) {
         SNG_WSTAMP(0);
         place(e0_, E, lane);
-        const int part = lane % L;
-        const int c0 = part * CPL;
-        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
         [[maybe_unused]] const size_t plane = (size_t)t * NC * (size_t)E;   // this step's timeline planes
         [[maybe_unused]] const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1
         [[maybe_unused]] const int Ad = p.act_dim;
@@ -193,27 +157,21 @@ struct WideGroup {
         }
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
-            // charger `charger(part, j)` (past a ragged lane's range: its charger NC - 1 again, discarded)
-            const uint32_t v4 = row_of(j, nc, E), r4 = r4_of(j, E), v8 = 2u * v4, r8 = 2u * r4;
+            // charger `charger(part, j)`
+            const uint32_t v4 = row_of(j), r4 = r4_of(j, E), v8 = 2u * v4, r8 = 2u * r4;
             if constexpr (STEP) {
                 if (PK) {   // 2 B records in charger quads: the lane's whole quads as 8 B, its last-pair charger as 2 B
-                    if constexpr (kQuads) {
-                        if (j < H && (j & 3) == 0)
-                            unpack_quad(bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)j * (uint32_t)E * 2u),
-                                        w + j);
-                        if (j == H) w[j] = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
-                    } else {
-                        const int cr = charger(part, j) < NC ? charger(part, j) : NC - 1;
-                        const RecOff ro = rec_off(cr, NC, E, el1);
-                        w[j] = bld16(rec_t, ro.v, ro.s);
-                    }
+                    if (j < H && (j & 3) == 0)
+                        unpack_quad(bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)j * (uint32_t)E * 2u),
+                                    w + j);
+                    if (j == H) w[j] = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
                 } else {
                     w[j] = bld(s.word + plane, v4, r4);
                     aux[PK ? 0 : j] = bld(s.aux + plane, v8, r8);
                 }
             }
             // a pair's 16 B once both its records are issued; the last pair's 8 B
-            if constexpr (STATE) issue_soc(j, lane, E, s);
+            if constexpr (STATE) issue_soc(j, E, s);
             if constexpr (STEP)
                 if (REQ) req[REQ ? j : 0] = bld(s.req + plane, v8, r8);
         }
@@ -232,14 +190,14 @@ struct WideGroup {
     // as they lie in memory (the lane's quads and its last-pair record: rq, rl; take_step_inputs unpacks them
     // into w[] once the step before has read its own), the requested SoC, and the step's table constants
     // (uniform loads through s.tables: a per-launch StepConst cannot carry T steps).
-    static constexpr int NQ = kQuads ? H / 4 : 1;
+    static constexpr int NQ = H / 4;
     uint64_t rq[NQ];
     uint32_t rl;
     double reqn[REQ ? CPL : 1];
     StepConst kn;
     __device__ __forceinline__ void issue_step_inputs(const float *act, int64_t E, int t, int vec_io, const Params &p,
                                                       const DeviceState &s, int lane) {
-        static_assert(PK && kQuads, "the day kernel steps packed days of stations whose lanes own whole record quads");
+        static_assert(PK, "the day kernel steps packed days");
         const size_t plane = (size_t)t * NC * (size_t)E;
         const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1, as issue()
 #pragma unroll
@@ -251,7 +209,7 @@ struct WideGroup {
         rl = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
         if constexpr (REQ) {
 #pragma unroll
-            for (int j = 0; j < CPL; ++j) reqn[j] = bld(s.req + plane, 2u * row_of(j, CPL, E), 2u * r4_of(j, E));
+            for (int j = 0; j < CPL; ++j) reqn[j] = bld(s.req + plane, 2u * row_of(j), 2u * r4_of(j, E));
         }
     }
     __device__ __forceinline__ void take_step_inputs() {
@@ -280,8 +238,6 @@ struct WideGroup {
         const int Ad = p.act_dim, O = p.obs_dim;
         const int le = lane / L, part = lane % L;
         const bool leader = part == 0;
-        const int c0 = part * CPL;
-        const int nc = kPairs ? CPL : ((NC - c0) < CPL ? NC - c0 : CPL);
         const size_t plane = (size_t)t * NC * (size_t)E;
         const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;
         const float *a_row = s_act + le * Ad;
@@ -293,8 +249,7 @@ struct WideGroup {
         uint32_t amax_bits = 0u;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
-            const int c = charger(part, j);
-            av[j] = a_row[c < NC ? c : NC - 1];
+            av[j] = a_row[charger(part, j)];
             amax_bits = __builtin_elementwise_max(amax_bits, __builtin_bit_cast(uint32_t, av[j]));
         }
         const bool not_nonneg = amax_bits > 0x7f800000u;
@@ -316,38 +271,29 @@ struct WideGroup {
             // charger discharges (charger_step<..., NONNEG>)
             double seq_pos = 0.0, pmin = __builtin_inf();
             int n_pos = 0;
-            double qv[L > 1 ? CPL : 1], sv[CPL];
+            double qv[CPL], sv[CPL];
             if (live) {
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     const int c = charger(part, j);
-                    if (!kPairs && NC % L != 0 && j >= nc) {   // a ragged lane's range ends: adds nothing
-                        qv[L > 1 ? j : 0] = 0.0;
-                        continue;
-                    }
+                    // visit_charger's conventions by hand: with the helper here the day kernel spills more SGPRs
+                    // than tests/test_day_kernel_resources.py allows (profiles/charger_visit_ab.txt)
                     const uint32_t capi = cap_field<PK>(w[j]);
                     const bool occ = (w[j] & W_OCC) != 0;
-                    const ChargerResult r = charger_step<true, true, kNonneg, PK>(p, PK ? (w[j] & ~W_STATIC) : w[j],
+                    const ChargerResult r = charger_step<true, kNonneg, PK>(p, PK ? (w[j] & ~W_STATIC) : w[j],
                                                                            PK ? 0.0 : aux[PK ? 0 : j], run_[j], req_of(j, p),
                                                                            av[j], t, recip_cap((double)capi));
                     sv[j] = (PK && !occ) ? (double)rec_soc(w[j]) : r.soc;
-                    if constexpr (KEEP) {
-                        run_[j] = sv[j];
-                    } else if constexpr (kPairs) {   // a pair's 16 B once both its chargers are stepped; the last pair's 8 B
-                        if (j < H && (j & 1))
-                            bst2<kNT>(s.soc, soc_a, sv[j - 1], sv[j], (uint32_t)(j - 1) * (uint32_t)E * 8u);
-                        if (j == H) bst<kNT>(s.soc, soc_b, sv[j], (uint32_t)(NC - 2) * (uint32_t)E * 8u);
-                    } else {
-                        bst<kNT>(s.soc, (uint32_t)soc_index(c, el1, NC, E) * 8u, sv[j]);
-                    }
+                    if constexpr (KEEP) run_[j] = sv[j];
+                    else store_soc(j, E, s, sv);
                     o_row[k_soc + c] = (float)r.soc;
                     o_row[k_soc + NC + c] = departure_obs<PK>((PK && !occ) ? 0u : w[j]);
                     n_nonexist += r.nx;
                     fl |= r.fl;
-                    if (L > 1) qv[L > 1 ? j : 0] = r.q;
-                    // the lane's own penalties in charger order; kPairs: the last pair's come after the other
-                    // lane's whole pairs (gather, below)
-                    if (!kPairs || j < H) pen_v += r.q;
+                    qv[j] = r.q;
+                    // the lane's own penalties in charger order; the last pair's come after the other lane's
+                    // whole pairs (below)
+                    if (j < H) pen_v += r.q;
                     const bool ip = r.pw > 0.0;
                     seq_pos += r.pw;   // >= 0 here (the float32 product of a >= 0, or 0.0): adding it is exact
                     n_pos += ip ? 1 : 0;
@@ -361,40 +307,32 @@ struct WideGroup {
             }
             // numpy sums fewer than 8 positive powers in order: one lane's running sum is that sum; two lanes'
             // partial sums combined are that sum only when one of them is empty or the sum is exact
-            bool split = false;
-            if constexpr (L > 1) {
-                // the other lanes' totals (exact combinations), and their penalties after the first lane's own,
-                // in charger order (adding a +0.0 term is exact)
-                const double seq_own = seq_pos, pmin_own = pmin;
-                const int n_own = n_pos;
-                const uint32_t nx_own = n_nonexist, fl_own = fl;
-                int with_pos = n_own > 0 ? 1 : 0;
-                auto gather = [&](auto kc) {
-                    constexpr int K = decltype(kc)::value;
-                    const int nk = (int)from_part<L, K>((uint32_t)n_own);
-                    with_pos += nk > 0 ? 1 : 0;
-                    n_pos += nk;
-                    seq_pos += from_part<L, K>(seq_own);
-                    pmin = __builtin_fmin(pmin, from_part<L, K>(pmin_own));
-                    n_nonexist += from_part<L, K>(nx_own);
-                    fl |= from_part<L, K>(fl_own);
+            // the other lane's totals (exact combinations), and its penalties after the first lane's own, in
+            // charger order (adding a +0.0 term is exact)
+            const double seq_own = seq_pos, pmin_own = pmin;
+            const int n_own = n_pos;
+            const uint32_t nx_own = n_nonexist, fl_own = fl;
+            int with_pos = n_own > 0 ? 1 : 0;
+            auto gather = [&] {
+                const int nk = (int)from_part<1>((uint32_t)n_own);
+                with_pos += nk > 0 ? 1 : 0;
+                n_pos += nk;
+                seq_pos += from_part<1>(seq_own);
+                pmin = __builtin_fmin(pmin, from_part<1>(pmin_own));
+                n_nonexist += from_part<1>(nx_own);
+                fl |= from_part<1>(fl_own);
 #pragma unroll
-                    for (int j = 0; j < (kPairs ? H : CPL); ++j) {
-                        const double qk = from_part<L, K>(qv[L > 1 ? j : 0]);
-                        pen_v = leader ? pen_v + qk : pen_v;
-                    }
-                };
-                gather(std::integral_constant<int, 1>{});
-                if constexpr (L > 2) {
-                    gather(std::integral_constant<int, 2>{});
-                    gather(std::integral_constant<int, 3>{});
+                for (int j = 0; j < H; ++j) {
+                    const double qk = from_part<1>(qv[j]);
+                    pen_v = leader ? pen_v + qk : pen_v;
                 }
-                if constexpr (kPairs) {   // the last pair: charger N - 2 (this lane), then N - 1 (the other)
-                    const double qk = from_part<L, 1>(qv[L > 1 ? H : 0]);
-                    pen_v = leader ? (pen_v + qv[L > 1 ? H : 0]) + qk : pen_v;
-                }
-                split = with_pos > 1;
+            };
+            gather();
+            {   // the last pair: charger N - 2 (this lane), then N - 1 (the other)
+                const double qk = from_part<1>(qv[H]);
+                pen_v = leader ? (pen_v + qv[H]) + qk : pen_v;
             }
+            const bool split = with_pos > 1;
             p_ch = seq_pos;
             const bool pos_slow = live && leader && (n_pos >= 8 || split) && !(seq_pos <= pmin * 0x1.0p28);
             if (__builtin_amdgcn_ballot_w64(pos_slow)) {   // wave-uniform: rare
@@ -425,7 +363,7 @@ struct WideGroup {
             // too), so the wavefront's SoC registers go to memory before it and come back after it; the
             // wavefront's own stores and loads of an address stay in order (one L1 for the whole wavefront)
             if constexpr (KEEP) {
-                store_state_soc(E, s, lane);
+                store_state_soc(E, s);
                 wave_mem_fence();
             }
             if (live && leader) {
@@ -438,13 +376,11 @@ struct WideGroup {
                     const double auxc = PK ? 0.0 : bld(s.aux + plane, el8, r8);
                     const double runc = bld(s.soc, so.v, so.s);
                     const double reqc = REQ ? bld(s.req + plane, el8, r8) : req_default(p);
-                    const uint32_t capi = cap_field<PK>(wc);
-                    const bool occ = (wc & W_OCC) != 0;
-                    const ChargerResult r = charger_step<true, true, false, PK>(p, PK ? (wc & ~W_STATIC) : wc, auxc, runc,
-                                                                                reqc, a_row[c], t, recip_cap((double)capi));
-                    bst<kNT>(s.soc, so.v, (PK && !occ) ? (double)rec_soc(wc) : r.soc, so.s);
-                    o_row[k_soc + c] = (float)r.soc;
-                    o_row[k_soc + NC + c] = departure_obs<PK>((PK && !occ) ? 0u : wc);
+                    const ChargerVisit<PK> v = visit_charger<true, false, PK>(p, wc, auxc, runc, reqc, a_row[c], t);
+                    const ChargerResult &r = v.r;
+                    bst<kNT>(s.soc, so.v, v.soc, so.s);
+                    o_row[k_soc + c] = v.obs_soc();
+                    o_row[k_soc + NC + c] = v.obs_dep();
                     n_nonexist += r.nx;
                     fl |= r.fl;
                     pen_v += r.q;
@@ -457,7 +393,7 @@ struct WideGroup {
             if constexpr (KEEP) {
                 wave_mem_fence();
 #pragma unroll
-                for (int j = 0; j < CPL; ++j) issue_soc(j, lane, E, s);
+                for (int j = 0; j < CPL; ++j) issue_soc(j, E, s);
             }
         }
         SNG_WSTAMP(2);
@@ -475,13 +411,14 @@ struct WideGroup {
     }
 };
 
-// L lanes per env (1, 2 or 4): lane `part` of an env steps chargers [part * CPL, min(NC, (part + 1) * CPL)),
-// CPL = ceil(NC / L).  The env's lanes are adjacent (one DPP quad); the partial charging sums, counts and
+// Two lanes per env (L = 2, the only layout compiled; the template parameter names the kernels): lane `part` of
+// an env steps chargers [part * H, (part + 1) * H), H = (NC - 2) / 2, and charger NC - 2 + part of the last pair
+// (WideGroup, above).  The env's lanes are adjacent (half a DPP quad); the partial charging sums, counts and
 // minima combine exactly on the first lane (a sum the exactness test accepts is exact in any order, and
 // fewer than 8 powers are numpy's in-order sum when one lane holds them all), the first lane adds the
-// other lanes' vehicle penalties after its own in charger order (Python's sum, penaliser.py:55), and the
-// rare exact-order paths run on the first lane over all chargers.  One group of 64 / L envs per wavefront;
-// the register budget is sized for L waves per SIMD (every wave of the E = 65,536 grid resident at once).
+// other lane's vehicle penalties after its own in charger order (Python's sum, penaliser.py:55), and the
+// rare exact-order paths run on the first lane over all chargers.  One group of 32 envs per wavefront;
+// the register budget is sized for two waves per SIMD (every wave of the E = 65,536 grid resident at once).
 // Measured and reverted (A/B on one box):
 //   - two groups of 32 envs per wavefront at N = 10 (1,024 wavefronts, each group's loads issued before the
 //     first group is stepped): 8.62-8.64 us per step in the graph against 6.68-6.71 us
@@ -496,7 +433,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) v
 step_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *__restrict__ reward,
                  uint8_t *__restrict__ done, int64_t E, int t, int vec_io, StepConst k, Params p, DeviceState s,
                  InfoPtrs info) {
-    static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per env");
     using Grp = WideGroup<NC, L, PK, REQ, NOISE>;
     using Lay = WideLds<NC, L>;
     extern __shared__ __attribute__((aligned(16))) float lds[];

@@ -9,7 +9,7 @@ The env, the actions and the graph shape are bench.py's (device-RNG days, `graph
 return accumulated, no per-env flag array).  Each round replays the step-node graph for `days` days, then the
 default graph, each between HIP events on the graphs' stream after `warmup` days of its own; one JSON line per
 round with the device time per day of both forms, then one summary line.  With SNG_LIBRARY pointing at another
-build of this source (say one compiled with day_prefetch() returning false) it measures that build the same way.
+build of this source it measures that build the same way.
 A station without a day kernel reports the same form twice (step_nodes_per_day says so)."""
 import argparse
 import json
