@@ -144,6 +144,33 @@ def test_steps_only_graph_matches_eager_over_a_generated_day_and_its_replay():
     w.close()
 
 
+def test_replayed_day_with_a_requested_soc_plane():
+    """A replayed day of a station with the requested SoC enabled: the replay clears the requests (req_zero), so
+    the plan drops REQ and the day kernel is the one without the stream, on a day whose req plane exists."""
+    E = 70
+    kw = dict(KW10, enable_requested_state_of_charge=True)
+    acts = make_actions(24, E, 11, seed=10)
+    v = SmartNanogridVecEnv(E, seed=11, rng="device", **kw)
+    w = SmartNanogridVecEnv(E, seed=11, rng="device", **kw)
+    for x in (v, w):
+        x.reset_tensors()
+        assert x.step_kernel_name() == "void sng::step_wide_kernel<10, 2, true, true, false>"
+        for t in range(24):   # the generated day itself, with its requests
+            x.step_tensors(acts[t])
+        x.replay_tensors()
+        assert x.step_kernel_name() == "void sng::step_wide_kernel<10, 2, true, false, false>"
+    g = EpisodeGraph(v, acts, with_reset=False)
+    assert g.step_nodes_per_day == 1
+    g.launch()
+    for t in range(24):
+        w.step_tensors(acts[t])
+    assert_same(v, w, "steps-only graph of a replayed day with a req plane")
+    assert bool((v.return_d != 0).any())
+    g.close()
+    v.close()
+    w.close()
+
+
 @pytest.fixture()
 def square_mode():
     O.lib().orc_set_square_mode.argtypes = [ctypes.c_int]

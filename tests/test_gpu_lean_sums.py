@@ -10,6 +10,10 @@ V2X stations (8+ negative powers), ordinary Box actions -- and require:
     same days and actions, for every env, and against the CPU oracle for a sample of envs;
   - the slow branch to have been needed, and to have mattered (the running sum differs from numpy's
     pairwise sum) in some env-steps, judged from the per-charger powers the diagnostics kernel reports.
+
+The wide step kernel (csrc/sng_step_wide.h; N = 10 without V2X, N = 50) keeps such sums per lane in its fast loop,
+which a wavefront takes only when none of its charger actions carries a sign bit: the second test drives that
+loop and its rebuild branch with a recipe laid out in whole wavefronts (wide_rebuild_cases.py).
 """
 import ctypes
 
@@ -22,6 +26,11 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from smart_nanogrid_gym import SmartNanogridVecEnv  # noqa: E402
+from smart_nanogrid_gym.vec_env import EpisodeGraph  # noqa: E402
+from test_gpu_bench_kernel import load_day  # noqa: E402
+from test_gpu_day_kernel import assert_same  # noqa: E402
+from wide_rebuild_cases import (E as RE, SEED as RSEED, STATIONS, RebuildCount, rebuild_actions,  # noqa: E402
+                                step_prices)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -60,8 +69,11 @@ def _seq(x):
 @pytest.mark.parametrize("N,v2x", [(10, True), (16, True), (8, True), (10, False), (16, False), (50, True), (50, False)])
 def test_lean_totals_vs_general_kernel_and_oracle(N, v2x):
     """N = 50 is BASELINE config 5's station (15-minute steps, extended day, stochastic profiles), stepped by
-    the wide lean kernel: running sums where exact, the positive powers rebuilt from the records and the
-    actions where not, and a wavefront with a discharging action in numpy's order throughout."""
+    the wide kernel, as is the N = 10 station without V2X.  These rows drive the wide kernel's general order
+    only: _actions puts -0.0 into every fourth env, the wide kernel chooses per wavefront, and with this
+    recipe and these seeds 0 of the 3,072 (N = 10) and 0 of the 12,288 (N = 50) wavefront-steps stay in its
+    fast loop.  The fast loop's running sums and its rebuild of the positive powers from the records and the
+    actions are driven by test_wide_fast_loop_rebuild_vs_general_kernel_and_oracle below."""
     E, seed = 2048, 4242 + N
     kw = dict(number_of_chargers=N, time_interval="1h", charging_mode="bounded",
               vehicle_uncharged_penalty_mode="sparse", pv_system_available_in_model=True,
@@ -116,3 +128,63 @@ def test_lean_totals_vs_general_kernel_and_oracle(N, v2x):
         assert need_neg > 0, need_neg
     lean.close()
     diag.close()
+
+
+@pytest.mark.parametrize("station", sorted(STATIONS))
+def test_wide_fast_loop_rebuild_vs_general_kernel_and_oracle(station):
+    """The wide kernel's fast loop with tiny positive actions (wide_rebuild_cases.py): wavefronts without a sign
+    bit keep running sums, and env-steps whose sums are not provably exact rebuild the positive powers from the
+    records and the actions tile (pos_slow in WideGroup::run) -- unpacked and packed records, and in the day
+    kernel, whose actions tile is the current step's while the next step's inputs already sit in registers.
+    Every env is bit-exact against the info=True twin and against the oracle (seeded seed + i, so config 5's
+    profile factors match); the twin's per-charger powers show that the rebuild was needed, that it changed the
+    sum, and that the change reached some env-step's reward (RebuildCount)."""
+    kw, rng, kernel, day_kernel = STATIONS[station]
+    wide = SmartNanogridVecEnv(RE, seed=RSEED, rng=rng, **kw)
+    diag = SmartNanogridVecEnv(RE, seed=RSEED, rng=rng, info=True, **kw)
+    diag._enable_info(per_charger=True)
+    graphed = SmartNanogridVecEnv(RE, seed=RSEED, rng=rng, **kw) if day_kernel else None
+    cfg = O.OracleConfig(**kw)
+    N, T = cfg.N, wide.timesteps
+    acts = rebuild_actions(N, T)
+    acts_d = torch.from_numpy(acts).to(wide.device)
+    envs = [O.OracleEnv(cfg, RSEED + e) for e in range(RE)]
+    count = RebuildCount(N, cfg.dt)
+    for day in range(2):
+        obs = wide.reset_tensors().cpu().numpy()
+        np.testing.assert_array_equal(obs, diag.reset_tensors().cpu().numpy())
+        assert wide.step_kernel_name() == kernel, wide.step_kernel_name()
+        if rng == "device":
+            ivs, ratios = wide.get_scenarios(0, RE)
+            ref0 = np.stack([load_day(e, iv, r, V=16) for e, iv, r in zip(envs, ivs, ratios)])
+        else:
+            ref0 = np.stack([e.reset() for e in envs])
+        np.testing.assert_array_equal(obs, ref0, err_msg=f"{station} day {day}: reset vs oracle")
+        if graphed is not None:
+            np.testing.assert_array_equal(graphed.reset_tensors().cpu().numpy(), obs)
+            g = EpisodeGraph(graphed, acts_d, with_reset=False)
+            assert g.step_nodes_per_day == 1
+            g.launch()
+        ret = np.zeros(RE)
+        for t in range(T):
+            what = f"{station} day {day} t {t}"
+            o, r, _ = wide.step_tensors(acts_d[t])
+            od, rd, _ = diag.step_tensors(acts_d[t])
+            o, r = o.cpu().numpy(), r.cpu().numpy()
+            np.testing.assert_array_equal(o, od.cpu().numpy(), err_msg=what + ": obs, wide vs general")
+            np.testing.assert_array_equal(r, rd.cpu().numpy(), err_msg=what + ": reward, wide vs general")
+            prices = step_prices(cfg, envs, t)
+            outs = [e.step(acts[t, i]) for i, e in enumerate(envs)]
+            np.testing.assert_array_equal(o, np.stack([x[0] for x in outs]), err_msg=what + ": obs vs oracle")
+            np.testing.assert_array_equal(r, np.array([x[1] for x in outs]), err_msg=what + ": reward vs oracle")
+            ret = ret + r
+            count.add_step(acts[t], diag.charger_power_d.cpu().numpy(), [x[3] for x in outs], prices)
+        np.testing.assert_array_equal(wide.battery_state_of_charge(), np.array([e.bess_soc for e in envs]))
+        np.testing.assert_array_equal(wide.return_d.cpu().numpy(), ret)
+        if graphed is not None:   # the day kernel: against the eager handle, which equals the oracle
+            assert_same(graphed, wide, f"{station} day {day}: day kernel vs eager steps")
+            g.close()
+    count.check(station)
+    for v in (wide, diag, graphed):
+        if v is not None:
+            v.close()
