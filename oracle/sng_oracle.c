@@ -606,8 +606,9 @@ static double charger_step(orc_env *e, orc_charger *ch, float a, int t, int *err
             ch->soc[t] = (1.0 < calc) ? 1.0 : calc;          /* min(calc, 1.0), :86 */
             power = p;
         } else {
-            /* over_discharging_flag = ceil(0.5 * (1 + sign(calc))) is 1 for calc >= 0 (:122) */
-            if (calc >= 0) power = -((soc * cap) / dt);     /* :128-132 */
+            /* over_discharging_flag = ceil(0.5 * (1 + sign(calc))) is 0 only for calc < 0 (:122); numpy's sign
+             * and ceil keep a NaN calc (a NaN action), NaN * 22 is NaN and `if NaN:` is true (:128) */
+            if (!(calc < 0)) power = -((soc * cap) / dt);   /* :128-132 */
             else power = p;
             ch->soc[t] = (calc > 0.0) ? calc : 0.0;         /* max(0.0, calc), :136 */
         }
@@ -696,7 +697,8 @@ int orc_env_step(orc_env *e, const float *actions, float *obs, orc_step_out *out
             double dp = (ba * 44) * 0.95;
             double calc = e->bess_soc + (dp * c->dt) / 80;
             e->bess_calc_power = dp;
-            if (calc < 0) dp = -((e->bess_soc * 80) / c->dt);          /* :82-94 */
+            /* the flag 1 - ceil(0.5 * (1 + sign(calc))) is 0 only for calc >= 0; NaN (a NaN action) is true */
+            if (!(calc >= 0)) dp = -((e->bess_soc * 80) / c->dt);      /* :82-94 */
             e->bess_soc = (calc > 0.0) ? calc : 0.0;
             e->bess_power = dp;
             rem = rem + dp;

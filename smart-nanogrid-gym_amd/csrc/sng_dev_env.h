@@ -106,9 +106,16 @@ __device__ __forceinline__ float departure_obs(uint32_t w) {
 // rounding midpoint and lies >= ulp/(2c) from one, while q' differs from x/c by < 2^-50 ulp,
 // so q' is the correctly rounded quotient -- bitwise equal to x / c.  Checked exhaustively for
 // every float32 mantissa and every c (tools/check_division.c; scaling by 2^k is exact).
+// That argument is about finite x, and the callers pass a magnitude: x >= +0.0 or NaN (charger_step takes the
+// sign off a discharging product and subtracts the quotient; IEEE division is symmetric in the sign).
+// x = +inf (the float32 charging product of an action of about 1.6e37 / dt and above overflows) has q = inf and
+// the remainder inf - inf = NaN, where x / c is inf.  So the remainder goes through min(remainder, q): for a
+// finite x the remainder (at most 2^-44 x) is below q >= x / 255, or both are +0, and it passes unchanged; for
+// x = inf v_min_f64 returns its other operand for the NaN, q = inf, and fma(inf, r, inf) is inf.  q is live
+// until the last fma anyway: no constant, no further register.  A NaN x stays NaN.
 __device__ __forceinline__ double div_by_cap(double x, double c, double r) {
     const double q = x * r;
-    return __builtin_fma(__builtin_fma(-q, c, x), r, q);
+    return __builtin_fma(__builtin_fmin(__builtin_fma(-q, c, x), q), r, q);
 }
 
 // 1/c for an integer capacity c in [1, 255]: v_rcp_f64 and one Newton step.  div_by_cap needs only a
@@ -140,8 +147,10 @@ struct ChargerResult {
 // (validated when a scenario is encoded).
 // FAST (NumPy-2 promotion and dt a power of two, e.g. the 1 h default) is straight-line code, so the
 // compiler interleaves the chargers of an env.
-// NONNEG: the caller knows a >= +0.0 (not NaN, not -0.0): the wide kernel's fast loop, which a wavefront
-// takes only when none of its actions is negative, -0.0 or NaN.  Then a vehicle either charges (a > 0) or idles, so the discharge
+// NONNEG: the caller knows a >= +0.0 (not NaN, not -0.0; +inf and anything above the Box included, no action is
+// clipped): the wide kernel's fast loop, which a wavefront takes only when none of its actions is negative, -0.0
+// or NaN.  An action whose float32 product overflows charges to SoC 1.0 and bills +inf (div_by_cap keeps the
+// infinite quotient).  Then a vehicle either charges (a > 0) or idles, so the discharge
 // branch -- the inverted-flag power (charger.py:122-132) and max(0, calc) -- is never selected and is not
 // computed; every value this returns equals the general form's for such actions.
 // PK: w is a device-RNG day's packed record (its capacity in bits 3-9), else a word.
@@ -162,35 +171,43 @@ __device__ __forceinline__ ChargerResult charger_step(const Params &p, uint32_t 
     const double cap = (double)capi;
     const bool idle = (a == 0.0f);
     const bool chg = (a > 0.0f);
-    double pc, change;
+    // calc: the SoC a charging action computes, prev + change; calc_dis: what a discharging action (a < 0, or NaN)
+    // computes, prev + change as well, from the magnitude of its change
+    static_assert(FAST || !NONNEG, "the NONNEG form is the wide kernel's: NumPy-2 promotion");
+    double pc, calc, calc_dis;
+    float pf = 0.0f;   // the float32 power (NumPy 2)
     if (!FAST && p.legacy) {   // NumPy < 2: float32 scalar * int -> float64 (float64 numerator: plain division)
         pc = ((double)a * p.ev_power) * p.ev_eff;
-        change = (pc * p.dt) / cap;
+        calc = calc_dis = prev + (pc * p.dt) / cap;
     } else {          // NumPy 2 (NEP 50): float32 product
-        const float pf = __fmul_rn(__fmul_rn(a, p.ev_power_f), p.ev_eff_f);
+        pf = __fmul_rn(__fmul_rn(a, p.ev_power_f), p.ev_eff_f);
         const float pdt = __fmul_rn(pf, p.dt_f);
         pc = (double)pf;
-        // exact reciprocal-fma division with rcap ~ 1/c (the LDS table, or recip_cap): the IEEE quotient
-        change = div_by_cap((double)pdt, cap, rcap);
+        // exact reciprocal-fma division with rcap ~ 1/c (the LDS table, or recip_cap): the IEEE quotient, +-inf
+        // for an infinite product
+        const double mag = div_by_cap(NONNEG ? (double)pdt : __builtin_fabs((double)pdt), cap, rcap);
+        calc = prev + mag;
+        calc_dis = prev - mag;
     }
-    const double calc = prev + change;
     if constexpr (NONNEG) {   // a > 0 charges, a == 0 idles (chg == !idle)
         const bool moved = occ && chg && p.bounded;
         o.soc = moved ? ((1.0 < calc) ? 1.0 : calc) : prev;
-        o.pw = moved ? pc : 0.0;
+        o.pw = (double)(moved ? pf : 0.0f);   // pc or 0.0, selected before the conversion: one select, not two
         o.nx = (!occ && chg) ? 1u : 0u;
         o.fl = (occ && chg && !p.bounded) ? (uint32_t)SNG_FLAG_CHARGING_MODE : 0u;
         return o;
     }
-    double pw_dis = pc;                                          // inverted flag, charger.py:122-132
+    // inverted flag, charger.py:122-132: ceil(0.5 * (1 + sign(calc))) * 22 is 0 only for calc < 0; a NaN calc (a
+    // NaN action) makes it NaN, which `if` takes for true, so a NaN action bills the finite clamp power
+    double pw_dis = pc;
     if (FAST) {
-        pw_dis = (calc >= 0.0) ? -((prev * cap) * p.rdt) : pc;
-    } else if (occ && !idle && !chg && calc >= 0.0) {
+        pw_dis = !(calc_dis < 0.0) ? -((prev * cap) * p.rdt) : pc;
+    } else if (occ && !idle && !chg && !(calc_dis < 0.0)) {
         const double x = prev * cap;
         pw_dis = -(p.dt_pow2 ? x * p.rdt : x / p.dt);
     }
     const double soc_chg = (1.0 < calc) ? 1.0 : calc;           // min(calc, 1.0)
-    const double soc_dis = (calc > 0.0) ? calc : 0.0;           // max(0.0, calc)
+    const double soc_dis = (calc_dis > 0.0) ? calc_dis : 0.0;   // max(0.0, calc)
     const bool moved = occ && !idle && p.bounded;
     o.soc = moved ? (chg ? soc_chg : soc_dis) : prev;
     o.pw = moved ? (chg ? pc : pw_dis) : 0.0;                   // full power billed when charging
@@ -259,7 +276,8 @@ __device__ __forceinline__ BessStep bess_step(const Params &p, const DeviceState
     b.pw = (ba * (b.chg ? p.bess_pmax_ch : p.bess_pmax_dis)) * (b.chg ? p.bess_eff_ch : p.bess_eff_dis);
     const double calc = bess + (b.pw * p.dt) / p.bess_cap;
     const double empty = bess * p.bess_cap;   // the over-discharge clamp's energy
-    b.dp = (calc < 0.0) ? -(p.dt_pow2 ? empty * p.rdt : empty / p.dt) : b.pw;
+    // :82-94: the flag 1 - ceil(0.5 * (1 + sign(calc))) is 0 only for calc >= 0; NaN for a NaN action, and true
+    b.dp = !(calc >= 0.0) ? -(p.dt_pow2 ? empty * p.rdt : empty / p.dt) : b.pw;
     if (ba == 0.0) {
         b.bpow = 0.0;
         b.bcalc = 0.0;

@@ -25,6 +25,9 @@ about 20 % forced to exactly 0 and 5 % forced to exactly the upper bound.
 
 Usage:  python tests/golden/make_golden.py        (rewrites tests/golden/*.npz, *.json)
         python tests/golden/make_golden.py eval   (only the evaluator replay cases, eval_*.npz)
+        python tests/golden/make_golden.py wild   (only the wild-action cases, wild_*.npz and wild_cases.json:
+                                                   actions outside the Box and non-finite, what the reference
+                                                   raises recorded; tests/wild_action_cases.py has the classes)
 """
 import builtins
 import json
@@ -357,6 +360,167 @@ def tables_fixture(Env, tmp):
     return out
 
 
+# ----------------------------------------------------------------------------------------
+# wild actions: outside the Box and non-finite (tests/wild_action_cases.py has the classes)
+# ----------------------------------------------------------------------------------------
+def _wild():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import wild_action_cases
+    return wild_action_cases
+
+
+def wild_actions(W, days, charger_classes, bess_classes, late_nan_steps=0):
+    """An action source for run_wild_case: the charger slots from `charger_classes`, the BESS slot from
+    `bess_classes` (one round-robin over the case's `days`, so that a case of short days holds every class);
+    late_nan_steps > 0 adds the NaN classes to the chargers at the day's last steps only (so that a day which a
+    NaN charger action ends has run its other classes first)."""
+    bess_pool = []
+
+    def acts(rng, env, T):
+        n = env.NUMBER_OF_CHARGERS
+        a = np.empty((T,) + env.action_space.shape, np.float32)
+        a[:, :n] = W.draw(rng, (T, n), charger_classes)
+        if late_nan_steps:
+            k = T - late_nan_steps
+            a[k:, :n] = W.draw(rng, (T - k, n), charger_classes + W.NANS)
+        if a.shape[1] > n:
+            if not bess_pool:
+                bess_pool.extend(W.draw(rng, (days * T,), bess_classes))
+            a[:, n] = [bess_pool.pop() for _ in range(T)]
+        return a
+    return acts
+
+
+def run_wild_case(Env, name, kwargs, seed, n_days, acts_of, fresh_env_per_day):
+    """run_case under wild actions, with what the reference raises recorded instead of propagated.
+
+    fresh_env_per_day: day d runs on a new env seeded seed + d (np.random.seed / random.seed), so nothing of a
+    day the reference left by an exception reaches the next one; otherwise one env seeded `seed` runs all days,
+    reset() between them.  A step that raises records nothing but its index and the exception; the day ends there
+    (n_steps[d] steps were recorded, the arrays' later rows stay 0).  An exception of the constructor or of reset()
+    is recorded as the case's whole result."""
+    meta = dict(name=name, kwargs=kwargs, seed=seed, n_days=n_days, fresh_env_per_day=bool(fresh_env_per_day),
+                after_raise="fresh env per day: day d is Env(**kwargs) after np.random.seed(seed + d); "
+                            "random.seed(seed + d)" if fresh_env_per_day else "no step of this case may raise",
+                raises=[], setup_error=None)
+    act_rng = np.random.default_rng(seed ^ 0x5EED)
+    env = None
+    rec = None
+    for day in range(n_days):
+        try:
+            if env is None or fresh_env_per_day:
+                s = seed + day if fresh_env_per_day else seed
+                np.random.seed(s)
+                random.seed(s)
+                env = Env(**kwargs)
+                cms = env.central_management_system
+                captured = {}
+
+                def spy(timestep, actions, ratio, _orig=cms.simulate, _cap=captured):
+                    _cap["res"] = _orig(timestep, actions, ratio)
+                    return _cap["res"]
+
+                cms.simulate = spy
+            T = int(24 / env.TIME_INTERVAL)
+            N = env.NUMBER_OF_CHARGERS
+            bess_before = cms.battery_system.current_state_of_charge if cms.battery_system else 0.0
+            obs0, _ = env.reset()
+        except Exception as exc:   # the reference cannot run this station at all
+            meta["setup_error"] = dict(day=day, type=type(exc).__name__, message=str(exc))
+            break
+        if rec is None:
+            O, A = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
+            meta.update(T=T, N=N, obs_dim=O, act_dim=A)
+            z = lambda *shape, dt=np.float64: np.zeros((n_days,) + shape, dt)
+            rec = dict(obs_reset=z(O, dt=np.float32), ratio=z(), bess_soc_reset=z(), soc0=z(N, 25), occ=z(N, 25),
+                       cap=z(N, 25), req=z(N, 25), arrivals=np.full((n_days, N, VMAX), -1, np.int64),
+                       departures=np.full((n_days, N, VMAX), -1, np.int64), actions=z(T, A, dt=np.float32),
+                       n_steps=z(dt=np.int64), obs=z(T, O, dt=np.float32), reward=z(T), done=z(T, dt=bool),
+                       charger_power=z(T, N), breakpoint=z(T, dt=np.int64), **{k: z(T) for k in RESULT_KEYS})
+        gv = cms.charging_station.generated_initial_values
+        rec["obs_reset"][day] = np.asarray(obs0, np.float32)
+        rec["ratio"][day] = env.random_pv_shift_ratio
+        rec["bess_soc_reset"][day] = bess_before
+        for k, key in (("soc0", "SOC"), ("occ", "Charger_occupancy"), ("cap", "Vehicle_capacities"),
+                       ("req", "Requested_SOC")):
+            rec[k][day] = np.array(gv[key], np.float64)
+        for c in range(N):
+            rec["arrivals"][day, c, :len(gv["Arrivals"][c])] = gv["Arrivals"][c]
+            rec["departures"][day, c, :len(gv["Departures"][c])] = gv["Departures"][c]
+        acts = acts_of(act_rng, env, T)
+        rec["actions"][day] = acts
+        for t in range(T):
+            del BREAKPOINTS[:]
+            try:
+                obs, reward, term, trunc, _ = env.step(acts[t].copy())
+            except Exception as exc:
+                meta["raises"].append(dict(day=day, step=t, type=type(exc).__name__, message=str(exc)))
+                break
+            r = captured["res"]
+            rec["obs"][day, t] = np.asarray(obs, np.float32)
+            rec["reward"][day, t] = float(reward)
+            rec["done"][day, t] = bool(term)
+            rec["charger_power"][day, t] = np.array(r["Charger power values"], np.float64)
+            rec["breakpoint"][day, t] = len(BREAKPOINTS)
+            for k, rk in RESULT_KEYS.items():
+                rec[k][day, t] = float(r[rk])
+            rec["n_steps"][day] = t + 1
+    return rec or {}, meta
+
+
+def wild_cases(W):
+    v2x = dict(vehicle_to_everything=True)
+    return [
+        # name, kwargs, seed, days, actions, fresh env per day
+        ("wild_v2x_bpv_n10", base_kwargs(**v2x), 101, 3, wild_actions(W, 3, W.ALL, W.ALL), False),
+        # dt = 0.25 h: the reference's 25-slot arrays (charger.py:16-19) do not hold a 96-step day; what it does
+        # instead is this case's result
+        ("wild_v2x_bess_15min_n4", base_kwargs(number_of_chargers=4, time_interval="15min",
+                                               pv_system_available_in_model=False, **v2x), 102, 1,
+         wild_actions(W, 1, W.ALL, W.ALL), False),
+        # dt = 2 h, which the reference does run: 1e37 overflows in the product's last factor only
+        ("wild_v2x_bess_2h_n10", base_kwargs(time_interval="2h",
+                                            pv_system_available_in_model=False, **v2x), 103, 3,
+         wild_actions(W, 3, W.ALL, W.ALL), False),
+        # no V2X: non-negative chargers, NaN only at the day's last three steps; the BESS takes every class
+        ("wild_bpv_n10", base_kwargs(), 104, 3, wild_actions(W, 3, W.NONNEG, W.ALL, late_nan_steps=3), True),
+        # no V2X, negative charger actions: the reference raises (central_management_system.py:158-159)
+        ("wild_neg_n4", base_kwargs(number_of_chargers=4), 105, 3, wild_actions(W, 3, W.ALL, W.ALL), True),
+    ]
+
+
+def main_wild(Env):
+    """tests/golden/wild_*.npz and wild_cases.json; no other fixture is touched."""
+    import warnings
+    W = _wild()
+    index = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # numpy's overflow / invalid value notices
+        for name, kw, seed, days, acts_of, fresh in wild_cases(W):
+            out, meta = run_wild_case(Env, name, kw, seed, days, acts_of, fresh)
+            if out:
+                # per class: how often it met an occupied charger, an empty one and the BESS in the recorded steps
+                N, cls = meta["N"], W.classify(out["actions"])
+                hit = {k: [0, 0, 0] for k in W.NAMES}
+                for d in range(days):
+                    for t in range(int(out["n_steps"][d])):
+                        occ = out["occ"][d][:, t] == 1
+                        for i, k in enumerate(W.NAMES):
+                            m = cls[d, t, :N] == i
+                            hit[k][0] += int((m & occ).sum())
+                            hit[k][1] += int((m & ~occ).sum())
+                            hit[k][2] += int((cls[d, t, N:] == i).sum())
+                meta["class_hits_occupied_empty_bess"] = hit
+                np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **out)
+            index.append(meta)
+            print(f"{name}: setup_error={meta['setup_error']} steps={out['n_steps'].tolist() if out else None} "
+                  f"raises={meta['raises']}")
+            if out:
+                print("   hits (occupied, empty, bess):", meta["class_hits_occupied_empty_bess"])
+    with open(os.path.join(HERE, "wild_cases.json"), "w") as fp:
+        json.dump(index, fp, indent=1)
+
+
 def main_eval(Env):
     index = []
     for name, kw, seed, models, eps, override in EVAL_CASES:
@@ -371,6 +535,12 @@ def main_eval(Env):
 
 def main():
     tmp = tempfile.mkdtemp(prefix="sng_golden_")
+    if sys.argv[1:] == ["wild"]:   # only the wild-action cases
+        try:
+            main_wild(import_reference(tmp))
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+        return
     if sys.argv[1:] == ["eval"]:   # only the evaluator replay cases
         try:
             main_eval(import_reference(tmp))
