@@ -296,14 +296,25 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
 
 /* `days` full days captured as one hipGraph: ([device-RNG reset] + the day's T steps) x days.
  * actions holds T consecutive [num_envs][act_dim] blocks (reused every day); obs/reward/done
- * are overwritten every step; info may be NULL.  Replays draw new days each time.
+ * are overwritten every step (but see SNG_GRAPH_TRAJECTORY); info may be NULL.  Replays draw new days each time.
  * Because every step's actions are known at capture and envs never interact, a day's T steps are one
- * graph node where the step plan has a day kernel (packed device-RNG days of the wide family's stations:
- * 10 chargers without V2X or stochastic profiles, and 50 chargers): each wavefront steps its envs through
- * the whole day with SoC, BESS SoC and the day return in registers, and still stores every step's
- * observation, reward, done and flags.  What is in memory after the graph has run is bit for bit what T
- * step nodes leave; only the intermediate SoC / BESS SoC / day return of steps before the last are never
- * written.  Every other plan, and SNG_GRAPH_STEP_NODES, captures T dependent step nodes.
+ * graph node where the step plan has a day kernel: each wavefront steps its envs through the whole day with
+ * SoC, BESS SoC and the day return in registers, and still stores every step's observation, reward, done and
+ * flags.  The plans with a day kernel (csrc/sng_step_plan.h, day_kernel_of):
+ *   - the lean family's (step_lean_kernel's stations: 1, 2, 4, 8 or 16 chargers, or 10 with V2X; no stochastic
+ *     profiles, no diagnostics, NumPy-2 promotion, a power-of-two dt), for device-RNG days and for
+ *     reference-RNG, injected and replayed days alike: day_lean_kernel;
+ *   - packed device-RNG days of the 10-charger station without V2X or stochastic profiles: day_wide_kernel,
+ *     which keeps only the last step's outputs, so not with SNG_GRAPH_TRAJECTORY.
+ * What is in memory after the graph has run is bit for bit what T step nodes leave; only the intermediate
+ * SoC / BESS SoC / day return of steps before the last are never written.  Every other plan (50 chargers, the
+ * general kernel's stations, any SngInfo diagnostics), and SNG_GRAPH_STEP_NODES, captures T dependent step
+ * nodes.
+ * SNG_GRAPH_TRAJECTORY keeps every step of every captured day instead of overwriting one block: obs is then
+ * [days][T + 1][num_envs][obs_dim] f32, reward [days][T][num_envs] f64 and done [days][T][num_envs] u8.  Block
+ * [d][0] of obs is day d's t = 0 observation: the graph's reset writes it with SNG_GRAPH_RESET, a steps-only
+ * graph leaves it to the caller.  Step t writes obs[d][t + 1], reward[d][t] and done[d][t]; day_returns and info
+ * are as without the flag.
  * flags: SNG_GRAPH_*; days > 1 needs SNG_GRAPH_RESET.
  * day_returns (device [days][num_envs] f64, may be NULL): day d's returns accumulate into row
  * d instead of info->episode_return, so a replay leaves every day's returns for one
@@ -315,6 +326,7 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
  * SNG_ERR_STATE. */
 #define SNG_GRAPH_RESET 1        /* start every day with a device-RNG reset */
 #define SNG_GRAPH_STEP_NODES 2   /* one graph node per step even where a day kernel exists (A/B, tests) */
+#define SNG_GRAPH_TRAJECTORY 4   /* obs / reward / done hold every step of every day (shapes above) */
 int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                      const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out);
 int sng_graph_launch(SngGraph *graph, void *stream);

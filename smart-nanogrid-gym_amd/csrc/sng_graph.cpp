@@ -33,22 +33,39 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     const int64_t E = env->E;
     const int A = p.act_dim;
     const int vec = (aligned16(actions) && aligned16(obs)) ? 1 : 0;
-    // a day's T steps as one day-kernel node where the plan has one (the wide family's packed days), else --
-    // or with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
-    g->day_kernel = !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip) != 0;
+    // SNG_GRAPH_TRAJECTORY: every step of every day keeps its outputs -- obs [days][T + 1][E][obs_dim] (block 0 of a
+    // day is the reset's observation), reward and done [days][T][E]; else every step overwrites one block
+    const bool traj = (flags & SNG_GRAPH_TRAJECTORY) != 0;
+    const size_t obs_block = (size_t)E * (size_t)p.obs_dim;
+    const int64_t obs_step = traj ? (int64_t)obs_block : 0, out_step = traj ? E : 0;
+    // a day's T steps as one day-kernel node where the plan has one (sng_step_plan.h day_kernel_of), else -- or
+    // with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
+    g->day_kernel = !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     for (int d = 0; e == hipSuccess && d < days; ++d) {
         InfoPtrs ipd = ip;   // day d's returns into row d (observe0 zeroes it, every step adds)
         if (day_returns) ipd.episode_return = day_returns + (size_t)d * E;
+        // day d's blocks: the reset's observation, then step 0's outputs
+        float *obs0 = obs + (traj ? (size_t)d * (size_t)(p.T + 1) * obs_block : 0);
+        float *obs_d = obs0 + obs_step;
+        double *reward_d = reward + (traj ? (size_t)d * (size_t)p.T * (size_t)E : 0);
+        uint8_t *done_d = done + (traj ? (size_t)d * (size_t)p.T * (size_t)E : 0);
         if (with_reset) {
-            e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs, ipd.episode_return, vec, cs);
+            e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs0, ipd.episode_return,
+                                (vec && aligned16(obs0)) ? 1 : 0, cs);
         }
         if (g->day_kernel) {
-            if (e == hipSuccess) e = launch_day(p, env->ds, ipd, actions, obs, reward, done, E, 0, p.T, vec, cs);
+            if (e == hipSuccess)
+                e = launch_day(p, env->ds, ipd, actions, obs_d, reward_d, done_d, E, 0, p.T,
+                               (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step);
             continue;
         }
-        for (int t = 0; e == hipSuccess && t < p.T; ++t)
-            e = launch_step(p, env->ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs, reward, done, E, t, vec, cs);
+        for (int t = 0; e == hipSuccess && t < p.T; ++t) {
+            float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
+            e = launch_step(p, env->ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs_t,
+                            reward_d + (size_t)t * (size_t)out_step, done_d + (size_t)t * (size_t)out_step, E, t,
+                            (vec && aligned16(obs_t)) ? 1 : 0, cs);
+        }
     }
     hipGraph_t graph = nullptr;
     hipError_t e2 = hipStreamEndCapture(cs, &graph);

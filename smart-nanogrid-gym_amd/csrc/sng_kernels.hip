@@ -34,7 +34,7 @@
 #include "sng_dev_env.h"        // one env's step arithmetic: charger, BESS, env tail
 #include "sng_step_lean.h"      // step_lean_kernel
 #include "sng_step_wide.h"      // step_wide_kernel
-#include "sng_step_day.h"       // day_wide_kernel
+#include "sng_step_day.h"       // day_wide_kernel, day_lean_kernel
 #include "sng_step_general.h"   // step_kernel
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
 
@@ -192,11 +192,14 @@ hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &in
                          vec_io, k, p, s, info);
 }
 
-// The day kernel of a plan: the packed days of the wide family's 10-charger station (sng_step_day.h); every other
-// plan has none.  N = 50 is not compiled: with every charger's SoC kept next to the step's 239 VGPRs it spills
-// (325-423 VGPR spills, 0.8-1 KB of scratch), so config 5's days stay T step nodes.
+// The day kernel of a plan (day_kernel_of, sng_step_plan.h): day_wide_kernel for the packed days of the wide
+// family's 10-charger station, day_lean_kernel for the lean family's plans (sng_step_day.h); every other plan has
+// none.  N = 50 is not compiled: with every charger's SoC kept next to the step's 239 VGPRs it spills (325-423 VGPR
+// spills, 0.8-1 KB of scratch), so config 5's days stay T step nodes.
 typedef void (*DayKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, Params, DeviceState,
                           InfoPtrs);
+typedef void (*DayLeanKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, int64_t, int64_t,
+                              Params, DeviceState, InfoPtrs);
 template <int NC>
 static StepLaunch day_launch(const StepPlan &pl, int64_t E, DayKernel &kern) {
     constexpr int L = kWideLanes;
@@ -206,21 +209,53 @@ static StepLaunch day_launch(const StepPlan &pl, int64_t E, DayKernel &kern) {
     kern = k[pl.req][pl.noise];
     return {nullptr, nullptr, blocks_for(E, Lay::WENVS), dim3(kWave), Lay::BYTES};
 }
+// an instantiation day_lean_compiled (sng_step_plan.h) leaves out is not instantiated
+template <int NC, bool PK, bool REQ>
+static DayLeanKernel day_lean_entry() {
+    if constexpr (day_lean_compiled(NC, PK, REQ)) return day_lean_kernel<NC, PK, REQ>;
+    else return nullptr;
+}
+template <int NC>
+static StepLaunch day_lean_launch(const StepPlan &pl, int64_t E, DayLeanKernel &kern) {
+    kern = day_lean_entry<NC, false, false>();
+    if (pl.pk && pl.req) kern = day_lean_entry<NC, true, true>();
+    else if (pl.pk) kern = day_lean_entry<NC, true, false>();
+    else if (pl.req) kern = day_lean_entry<NC, false, true>();
+    return {nullptr, nullptr, blocks_for(E, kLeanBlock), dim3(kLeanBlock), LeanLds<NC>::BYTES};
+}
 
-int day_kernel_available(const Params &p, const InfoPtrs &info) {
-    const StepPlan pl = step_plan(p, info_diag(info));
-    return (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10) ? 1 : 0;
+int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory) {
+    return day_kernel_of(step_plan(p, info_diag(info)), trajectory) != DAY_NONE ? 1 : 0;
 }
 
 hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream) {
-    if (!day_kernel_available(p, info)) return hipErrorNotSupported;
-    if (t0 < 0 || nt < 1 || t0 + nt > p.T) return hipErrorInvalidValue;
+                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
+                      int64_t obs_step, int64_t out_step) {
     const StepPlan pl = step_plan(p, info_diag(info));
-    DayKernel kern = nullptr;
-    const StepLaunch l = day_launch<10>(pl, E, kern);
+    const DayFamily fam = day_kernel_of(pl, obs_step != 0 || out_step != 0);
+    if (fam == DAY_NONE) return hipErrorNotSupported;
+    if (t0 < 0 || nt < 1 || t0 + nt > p.T) return hipErrorInvalidValue;
+    if (fam == DAY_WIDE) {
+        DayKernel kern = nullptr;
+        const StepLaunch l = day_launch<10>(pl, E, kern);
+        return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
+                             vec_io, p, s, info);
+    }
+    DayLeanKernel kern = nullptr;
+    StepLaunch l;
+    switch (pl.nc) {   // the lean sizes of kStationSizes
+        case 1: l = day_lean_launch<1>(pl, E, kern); break;
+        case 2: l = day_lean_launch<2>(pl, E, kern); break;
+        case 4: l = day_lean_launch<4>(pl, E, kern); break;
+        case 8: l = day_lean_launch<8>(pl, E, kern); break;
+        case 10: l = day_lean_launch<10>(pl, E, kern); break;
+        case 16: l = day_lean_launch<16>(pl, E, kern); break;
+    }
+    if (!kern) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
+    // every step's observation block 16 B aligned, or none is promised to be
+    if (obs_step % 4 != 0) vec_io = 0;
     return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
-                         vec_io, p, s, info);
+                         vec_io, obs_step, out_step, p, s, info);
 }
 
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len) {

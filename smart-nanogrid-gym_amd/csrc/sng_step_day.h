@@ -1,10 +1,14 @@
-// sng_step_day.h -- the day kernel (day_wide_kernel): the steps t0 .. t0 + nt - 1 of a packed (device-RNG) day in
-// one launch, for the wide family's stations.  sng_graph_create captures it in place of the day's T dependent
-// step_wide_kernel nodes: it is given every step's actions at capture, and envs never interact, so a wavefront
-// can step its 64 / L envs through the whole day on its own -- no grid-wide synchronisation, no node boundary
-// (1.6-1.9 us each, the end-of-kernel write-back the next node waits for included) and no state round trip.
-// Needs sng_step_wide.h (WideGroup: the step's arithmetic is run<KEEP = true>(), nothing is restated here).
-// Included by sng_kernels.hip only.
+// sng_step_day.h -- the day kernels: the steps t0 .. t0 + nt - 1 of a loaded day in one launch.  sng_graph_create
+// captures one in place of the day's T dependent step nodes: it is given every step's actions at capture, and envs
+// never interact, so a wavefront can step its envs through the whole day on its own -- no grid-wide synchronisation,
+// no node boundary (1.6-1.9 us each, the end-of-kernel write-back the next node waits for included) and no state
+// round trip.
+//   day_wide_kernel  packed (device-RNG) days of the wide family's 10-charger station, 64 / L envs per wavefront;
+//   day_lean_kernel  the lean family's stations, packed and unpacked days, 64 envs per wavefront; it can keep every
+//                    step's outputs (per-step strides).
+// Which plan has which is decided in sng_step_plan.h (day_kernel_of).
+// Needs sng_step_wide.h and sng_step_lean.h (WideGroup, LeanGroup: a step's arithmetic is their run<KEEP = true>(),
+// nothing is restated here).  Included by sng_kernels.hip only.
 #pragma once
 
 namespace sng {
@@ -58,6 +62,61 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
     }
     g.store_state(E, p, s, info, lane);
     bump_day_counter<true>(p, s, t0);
+}
+
+// day_lean_kernel: the same for the lean family's stations (step_lean_kernel's: N <= 16, one lane per env), for
+// both timeline encodings -- packed device-RNG days (PK) and the word / aux planes of reference-RNG, injected and
+// replayed days.  Geometry as step_lean_kernel's: one wavefront per workgroup, 64 envs per wavefront, LeanLds<NC>
+// and the same idle-lane convention.  The step is LeanGroup::run<KEEP = true>(), nothing is restated here; with the
+// SoC in registers a step's first store is the reward store of the env tail, and step t + 1's inputs are issued
+// ahead of it.
+//   once a day:  the PV ratio, BESS SoC, t = 0 penalty, day return and every charger's SoC (the 16 B pairs of
+//                sng_layout.h) are loaded before the first step; SoC, BESS SoC and the day return are stored after
+//                the last, bess0 is written at t = 0 and the day counter advanced once (bump_day_counter<PK>).
+//   every step:  the actions tile, record plane t + 1 (PK) or the word and aux planes of t, the requested-SoC
+//                plane (REQ) and the ten table constants are read; observation rows, reward, done, flags and the
+//                flag summary are stored as step_lean_kernel stores them.
+// obs_step / out_step: floats between two steps' observation blocks and elements between two steps' reward and
+// done blocks (SNG_GRAPH_TRAJECTORY: every step's outputs are kept), 0 when every step overwrites the same block.
+// vec_io promises 16 B alignment of every step's block, so the caller clears it when obs_step is no multiple of 4.
+//
+// Registers.  At 65,536 envs the grid is 1,024 wavefronts, one per SIMD, so a wavefront may take the whole
+// 512-entry file; smaller populations leave SIMDs empty.  Occupancy buys nothing here, and a spill would put
+// scratch traffic on the path this kernel exists to shorten: the kernel asks for one wavefront per SIMD at least
+// and bounds nothing above it (kDayLeanWaves), which leaves the allocator free to use what the prefetch needs
+// (N = 16 unpacked with the requested SoC: 16 + 32 + 32 VGPRs of step t + 1's inputs next to run_[]'s 32).
+// tests/test_day_lean_kernel_resources.py holds every instantiation to zero scratch and zero VGPR spills.
+constexpr int kDayLeanWaves = 1;
+template <int NC, bool PK, bool REQ>
+__global__ __launch_bounds__(kLeanBlock) __attribute__((amdgpu_waves_per_eu(kDayLeanWaves))) void
+day_lean_kernel(const float *__restrict__ act, float *__restrict__ obs, double *__restrict__ reward,
+                uint8_t *__restrict__ done, int64_t E, int t0, int nt, int vec_io, int64_t obs_step, int64_t out_step,
+                Params p, DeviceState s, InfoPtrs info) {
+    static_assert(kLeanBlock == kWave, "one wavefront per workgroup");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x;
+    const LeanTiles<NC> tl(lds, 0);
+    LeanGroup<NC, PK, REQ> g;
+    const size_t block = (size_t)E * (size_t)p.act_dim;    // one step's actions
+    g.template issue<true, false>((int64_t)blockIdx.x * kLeanBlock, act, E, t0, vec_io, p, s, info, lane);   // the day's state
+    g.issue_step_inputs(act, E, t0, vec_io, p, s, lane);
+    const int t1 = t0 + nt;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        g.take_step_inputs(p);
+        g.act_tile.commit(tl.s_act, lane);
+        wave_lds_fence();
+        const StepConst k = g.kn;
+        if (t + 1 < t1)   // ahead of this step's stores
+            g.issue_step_inputs(act + (size_t)(t + 1 - t0) * block, E, t + 1, vec_io, p, s, lane);
+        g.template run<true>(tl.s_act, tl.s_obs, tl.s_pos, tl.s_neg, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
+        wave_lds_fence();   // the next step's tile writes stay behind this step's reads of both tiles
+        obs += obs_step;
+        reward += out_step;
+        done += out_step;
+    }
+    g.store_state(E, p, s, info);
+    bump_day_counter<PK>(p, s, t0);
 }
 
 }  // namespace sng

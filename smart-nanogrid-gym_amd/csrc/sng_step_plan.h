@@ -1,4 +1,5 @@
-// sng_step_plan.h -- which step kernel a handle's Params select, decided once.
+// sng_step_plan.h -- which step kernel a handle's Params select, and which day kernel a captured day of that plan
+// runs (day_kernel_of), each decided once.
 //
 // launch_step (sng_kernels.hip) dispatches the kernel a plan names and step_kernel_name formats the same plan
 // as the name rocprofv3 reports, so the two cannot disagree.  Host only, no HIP types: it compiles with plain
@@ -78,6 +79,42 @@ inline StepPlan step_plan(const Params &p, bool diag) {
         pl.lanes = kWideLanes;
     }
     return pl;
+}
+
+// Which day kernel (sng_step_day.h) a plan has: a captured day's T steps as one launch.  Decided here and nowhere
+// else: day_kernel_available and launch_day (sng_kernels.hip) both ask this.
+//   - the lean family's plans run day_lean_kernel<NC, PK, REQ>, at every compiled lean size and for both timeline
+//     encodings (but day_lean_compiled, below);
+//   - the wide family's packed days at N = 10 run day_wide_kernel<10, 2, REQ, NOISE>.  That kernel keeps no
+//     step's outputs but the last (it takes no per-step stride), so with `trajectory` the plan has none;
+//   - N = 50 (it would spill), the wide family's unpacked days, the general kernel's plans and any plan with
+//     diagnostics have none: their days stay T step nodes.
+enum DayFamily : int { DAY_NONE, DAY_WIDE, DAY_LEAN };
+// day_lean_kernel<nc, pk, req> is compiled for every lean size and flag pair but one: every instantiation must
+// have zero scratch and zero VGPR spills (tests/test_day_lean_kernel_resources.py), and <1, true, true> -- one
+// charger, packed days, the requested-SoC stream -- is left with a 36 B private segment by ROCm 7.2's LLVM (138
+// VGPRs, 76 SGPR spills into VGPR lanes, no VGPR spill; a 32 B SGPR spill slot that no instruction uses survives
+// frame lowering, whatever the occupancy attribute and the order of the loads).  Its plan keeps T step nodes.
+constexpr bool day_lean_compiled(int nc, bool pk, bool req) { return !(nc == 1 && pk && req); }
+inline DayFamily day_kernel_of(const StepPlan &pl, bool trajectory) {
+    const StationSize *sz = station_size(pl.nc);
+    if (pl.diag || !sz) return DAY_NONE;
+    if (pl.family == STEP_LEAN && sz->lean) return day_lean_compiled(pl.nc, pl.pk, pl.req) ? DAY_LEAN : DAY_NONE;
+    if (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10 && !trajectory) return DAY_WIDE;
+    return DAY_NONE;
+}
+// The name rocprofv3 reports for a plan's day kernel; an empty string where it has none.
+inline int day_plan_name(const StepPlan &pl, bool trajectory, char *buf, int len) {
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    switch (day_kernel_of(pl, trajectory)) {
+        case DAY_LEAN:
+            return snprintf(buf, (size_t)len, "void sng::day_lean_kernel<%d, %s, %s>", pl.nc, b(pl.pk), b(pl.req));
+        case DAY_WIDE:
+            return snprintf(buf, (size_t)len, "void sng::day_wide_kernel<%d, %d, %s, %s>", pl.nc, pl.lanes, b(pl.req),
+                            b(pl.noise));
+        default: break;
+    }
+    return snprintf(buf, (size_t)len, "%s", "");
 }
 
 // The name rocprofv3 reports for a plan's kernel (bench.py looks its kernel-stats and PMC records up by it).

@@ -24,6 +24,7 @@ RNG_REFERENCE = 0
 RNG_DEVICE = 1
 GRAPH_RESET = 1        # sng.h SNG_GRAPH_RESET
 GRAPH_STEP_NODES = 2   # sng.h SNG_GRAPH_STEP_NODES
+GRAPH_TRAJECTORY = 4   # sng.h SNG_GRAPH_TRAJECTORY
 FLAG_NEGATIVE_DEMAND = 0x1
 FLAG_CHARGING_MODE = 0x2
 FLAG_BESS_SOC_ABOVE_1 = 0x4

@@ -918,9 +918,16 @@ class EpisodeGraph:
     """Whole days (device-RNG reset + T fused steps, x days) captured once as a hipGraph and
     replayed; actions come from a device tensor [T, E, act_dim] reused every day.  Where the station has a day
     kernel (include/sng.h, sng_graph_create) a day's T steps are one graph node; step_nodes=True keeps one
-    node per step (the same results; for A/B and tests)."""
+    node per step (the same results; for A/B and tests).
 
-    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False):
+    trajectory=True keeps every step's outputs instead of the last step's: the graph then writes
+    obs_traj [days, T + 1, E, obs_dim] float32, reward_traj [days, T, E] float64 and done_traj [days, T, E] uint8,
+    which this object allocates, and a launch does not write venv.obs_d, venv.reward_d or venv.done_d.
+    obs_traj[d, t] is the observation that step t's action answered (obs_traj[d, 0] is the reset's; a steps-only
+    graph copies venv.obs_d there at every launch), reward_traj[d, t] and done_traj[d, t] are step t's, and
+    obs_traj[d, t + 1] is the observation step t returned."""
+
+    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False, trajectory=False):
         """days > 1 captures that many consecutive days (each with its reset) in one graph,
         which amortises the graph launch.  day_returns: optional device tensor [days, E] f64;
         day d's returns accumulate into row d (instead of venv.return_d).  A seed left by seed() takes effect
@@ -932,6 +939,8 @@ class EpisodeGraph:
             raise ValueError("seed() waits for the next reset: reset before capturing a steps-only graph")
         self.venv = venv
         self.days = int(days)
+        self.with_reset = bool(with_reset)
+        self.trajectory = bool(trajectory)
         self.actions = actions.contiguous()
         self.day_returns = day_returns
         dr = None
@@ -940,14 +949,23 @@ class EpisodeGraph:
                     or day_returns.device != venv.device or not day_returns.is_contiguous()):
                 raise ValueError("day_returns must be a contiguous float64 device tensor [days, num_envs]")
             dr = ctypes.c_void_p(day_returns.data_ptr())
+        obs, reward, done = venv.obs_d, venv.reward_d, venv.done_d
+        self.obs_traj = self.reward_traj = self.done_traj = None
+        if self.trajectory:
+            T, E = venv.timesteps, venv.num_envs
+            self.obs_traj = obs = torch.zeros((self.days, T + 1, E, venv.obs_dim), dtype=torch.float32,
+                                              device=venv.device)
+            self.reward_traj = reward = torch.zeros((self.days, T, E), dtype=torch.float64, device=venv.device)
+            self.done_traj = done = torch.zeros((self.days, T, E), dtype=torch.uint8, device=venv.device)
         g = ctypes.c_void_p()
         with torch.cuda.device(venv.device):
             check(lib().sng_graph_create(venv._h, ctypes.c_void_p(self.actions.data_ptr()),
-                                         ctypes.c_void_p(venv.obs_d.data_ptr()),
-                                         ctypes.c_void_p(venv.reward_d.data_ptr()),
-                                         ctypes.c_void_p(venv.done_d.data_ptr()), ctypes.byref(venv._info),
+                                         ctypes.c_void_p(obs.data_ptr()),
+                                         ctypes.c_void_p(reward.data_ptr()),
+                                         ctypes.c_void_p(done.data_ptr()), ctypes.byref(venv._info),
                                          (_native.GRAPH_RESET if with_reset else 0)
-                                         | (_native.GRAPH_STEP_NODES if step_nodes else 0),
+                                         | (_native.GRAPH_STEP_NODES if step_nodes else 0)
+                                         | (_native.GRAPH_TRAJECTORY if self.trajectory else 0),
                                          self.days, dr, ctypes.byref(g)), venv._h)
         self._g = g
 
@@ -958,6 +976,12 @@ class EpisodeGraph:
 
     def launch(self, stream=None):
         s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)
+        if self.trajectory and not self.with_reset:   # the loaded day's t = 0 observation, ahead of the graph
+            if stream is None:
+                self.obs_traj[0, 0].copy_(self.venv.obs_d)
+            else:
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.venv.device)):
+                    self.obs_traj[0, 0].copy_(self.venv.obs_d)
         check(lib().sng_graph_launch(self._g, s), self.venv._h)
 
     def close(self):
