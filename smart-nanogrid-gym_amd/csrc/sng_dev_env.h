@@ -89,6 +89,17 @@ __host__ __device__ inline double step_constant(const Tables *tb, int t, int i) 
                       : i < CST_PV ? tb->price_norm[t + i - CST_PN] : i == CST_PV ? tb->pv_power[t] : tb->price[t];
 }
 
+// The same through the constant address space, for a kernel that stores between its steps (day_wide_kernel): no
+// kernel writes the tables, but the compiler cannot know that once the kernel has stored anything, and then
+// turns a uniform load of them into a vector load: 20 VGPRs per step's constants, counted in vmcnt between the
+// step's other loads and stores.  Constant-address-space loads are scalar loads (the scalar cache, lgkmcnt).
+__device__ __forceinline__ double step_constant_scalar(const Tables *tb, int t, int i) {
+    typedef const __attribute__((address_space(4))) double *ConstF64;
+    const double *q = i < CST_PN ? &tb->irr_norm[t + i]
+                                 : i < CST_PV ? &tb->price_norm[t + i - CST_PN] : i == CST_PV ? &tb->pv_power[t] : &tb->price[t];
+    return *(ConstF64)(uintptr_t)q;
+}
+
 // Remaining time to departure / 24 (smart_nanogrid_environment.py:207-208) as float32.
 // The reference rounds d / 24 in float64 and then to float32; for integers d < 256 that equals the
 // correctly rounded float32 quotient (d/24 is never a float32 rounding midpoint), which

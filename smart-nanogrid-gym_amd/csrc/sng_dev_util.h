@@ -153,7 +153,13 @@ __device__ __forceinline__ void copy_in(float *__restrict__ dst, const float *__
 // tile does not fit one round (count > 4 * K * BLOCK floats) issue() does nothing and commit()
 // falls back to copy_in.  Native vector types only (HIP's float4 wrapper keeps the array
 // from being promoted to registers).
-template <int K, int BLOCK>
+// VEC_ONLY: only the aligned form (16 B loads) is staged in registers; an unaligned tile goes through copy_in at
+// commit() whatever its size.  For a caller that issues in one loop iteration and commits in the next (the day
+// kernel): the compiler's wait insertion does not know that the two forms exclude each other, sees the
+// one-float loads of one iteration pending where the next overwrites the same registers with its 16 B loads,
+// and makes every wavefront wait there for all it has in flight.  (At the day kernel's geometry the one-float
+// form held only a last wavefront of at most 11 envs.)
+template <int K, int BLOCK, bool VEC_ONLY = false>
 struct TileStage {
     typedef float v4f __attribute__((ext_vector_type(4)));
     v4f v[K];
@@ -164,9 +170,9 @@ struct TileStage {
         src = s;
         count = cnt;
         vec = vec_io && (cnt & 3) == 0;
-        one_round = vec ? (cnt >> 2) <= K * BLOCK : cnt <= K * BLOCK;
+        one_round = vec ? (cnt >> 2) <= K * BLOCK : !VEC_ONLY && cnt <= K * BLOCK;
         if (!one_round) return;
-        if (vec) {
+        if (VEC_ONLY || vec) {
             const v4f *s4 = reinterpret_cast<const v4f *>(s);
             const int n4 = cnt >> 2;
 #pragma unroll
@@ -187,7 +193,7 @@ struct TileStage {
             copy_in<K, BLOCK>(dst, src, count, vec, tid);
             return;
         }
-        if (vec) {
+        if (VEC_ONLY || vec) {
             v4f *d4 = reinterpret_cast<v4f *>(dst);
             const int n4 = count >> 2;
 #pragma unroll
@@ -236,5 +242,14 @@ __device__ __forceinline__ void wave_mem_fence() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
+
+// Wait until every vector memory operation the wavefront has issued is complete: s_waitcnt vmcnt(0) (the
+// gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 left at their maxima).  vmcnt counts
+// loads and stores in issue order, and the compiler places the wait a loaded register needs at its first use,
+// with the count of the shortest path from the load to there.  In a loop that issues a load ahead of stores and
+// uses it an iteration later, that shortest path is the loop's entry, where no store is in between: on the back
+// edge the same count makes the use wait for the stores as well.  A caller that drains its loads explicitly
+// before its stores, on every path into the use, leaves the compiler nothing to wait for there.
+__device__ __forceinline__ void wave_vmem_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 }  // namespace sng

@@ -13,10 +13,17 @@
 
 namespace sng {
 
-// Step t + 1's loads (its actions tile, records, requested SoC and table constants) are issued before step t's
-// first store.  A store counts in vmcnt ahead of every later load, so a load issued behind step t's stores waits
-// for them; issued ahead of them it costs registers for the whole step (the raw records, the tile's registers
-// and, with the stream, the requested SoC).
+// Step t + 1's loads (its actions tile, records and requested SoC) are issued before step t's first store.  A
+// store counts in vmcnt ahead of every later load, so a load issued behind step t's stores waits for them; issued
+// ahead of them it costs registers for the whole step (the raw records, the tile's registers and, with the
+// stream, the requested SoC).  Issuing them early is half of it: the wait for them has to come before step t's
+// stores too.  The compiler puts a loaded register's wait at its first use -- the top of step t + 1 -- with the
+// count that is safe on the loop's entry, where no store lies between the load and the use; on the back edge that
+// count drains step t's stores as well (1.8 us of a 4.1 us step, profiles/day_kernel_chain_ab.txt).  So the
+// loads are drained explicitly where nothing younger is in flight (wave_vmem_drain: before the loop, and in
+// WideGroup::run<KEEP> between the chargers and the env tail's first store), the actions tile has only its
+// aligned form in registers (TileStage, VEC_ONLY) and the rare general path drains its SoC reloads: no path into
+// the loop's top, real or only in the control-flow graph, leaves a load pending there.
 // Geometry as step_wide_kernel's: one wavefront per workgroup, WideLds<NC, L>::WENVS envs per wavefront, the
 // same LDS tiles.  `act` is step t0's [E][act_dim] block, the later steps' blocks follow it.
 //   once a day:  the PV ratio, BESS SoC, t = 0 penalty, day return, profile keys and every charger's SoC are
@@ -24,8 +31,8 @@ namespace sng {
 //                stored after the last step, as the same f64 values memory would have carried from step to
 //                step.  bess0 is written at t = 0 and the day counter advanced once, as by the step kernel.
 //   every step:  the actions tile, record plane t + 1 (and the requested-SoC plane) are read, the table
-//                constants come from s.tables by uniform loads, and the observation rows, reward, done, flags
-//                and the flag summary are stored exactly as step_wide_kernel stores them.
+//                constants come from s.tables by scalar loads at the step's own top, and the observation rows,
+//                reward, done, flags and the flag summary are stored exactly as step_wide_kernel stores them.
 // Per env-step it reads 4 (N + 1) + 2 N bytes and writes 4 (2 N + 9) + 9; per env-day the state moves
 // 8 N + 32 bytes each way, plus bess0.
 template <int NC, int L, bool REQ, bool NOISE>
@@ -47,16 +54,34 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
 #pragma unroll
     for (int j = 0; j < 4; ++j) g.fpv[j] = g.fpr[j] = 1.0;
     g.issue_step_inputs(act, E, t0, vec_io, p, s, lane);
+    // the day's state and the first step's inputs landed before the loop, as every later step's are before the
+    // stores of the step ahead of it (WideGroup::run): nothing the loop's top uses is still in flight on either
+    // way into it, so no wait there stands behind a store
+    wave_vmem_drain();
+    // Which of a step's ten table constants go to vector registers (bit i: constant i, CST_*): all of them in the
+    // headline's instantiation; with the requested-SoC stream or the profile factors the first two and the env
+    // tail's two.  Chosen by what the register allocator makes of each instantiation, against the SGPR-spill
+    // ceilings of tests/test_day_kernel_resources.py (all ten there: 157 spills with the factors, and a stack
+    // slot with the stream)
+    constexpr unsigned kPinned = (REQ || NOISE) ? 0x303u : 0x3ffu;
     const int t1 = t0 + nt;
 #pragma unroll 1
     for (int t = t0; t < t1; ++t) {
-        const StepConst k = g.kn;
         g.take_step_inputs();
-        g.act_tile.commit(lds, lane);
+        g.day_tile.commit(lds, lane);
         wave_lds_fence();
         if constexpr (NOISE) expand_profile_factors(p, keys, t, g.fpv, g.fpr);
         if (t + 1 < t1)   // ahead of this step's stores
             g.issue_step_inputs(act + (size_t)(t + 1 - t0) * block, E, t + 1, vec_io, p, s, lane);
+        // this step's table constants: scalar loads, which wait on lgkmcnt and never behind a store, so they need
+        // no step of prefetch.  The pinned ones are copied to vector registers once loaded (an empty asm with a
+        // "v" operand): the kernel has vector registers to spare and none of the scalar ones
+        StepConst k;
+#pragma unroll
+        for (int i = 0; i < CST_COUNT; ++i) {
+            k.v[i] = step_constant_scalar(s.tables, t, i);
+            if (kPinned & (1u << i)) asm("" : "+v"(k.v[i]));
+        }
         g.template run<true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
         wave_lds_fence();   // the next step's tile writes stay behind this step's reads of both tiles
     }

@@ -186,23 +186,22 @@ struct WideGroup {
             ret_l = bld(info.episode_return ? info.episode_return : s.ratio, el8);
         }
     }
-    // One step's inputs of a packed day, for the day kernel: the actions tile into act_tile, the step's records
+    // One step's inputs of a packed day, for the day kernel: the actions tile into day_tile, the step's records
     // as they lie in memory (the lane's quads and its last-pair record: rq, rl; take_step_inputs unpacks them
-    // into w[] once the step before has read its own), the requested SoC, and the step's table constants
-    // (uniform loads through s.tables: a per-launch StepConst cannot carry T steps).
+    // into w[] once the step before has read its own) and the requested SoC.  The step's table constants are
+    // not among them: the day kernel reads them by scalar loads at the top of their own step
+    // (step_constant_scalar; a per-launch StepConst cannot carry T steps).
     static constexpr int NQ = H / 4;
+    TileStage<KT, kWave, true> day_tile;   // issued a step ahead of its commit: TileStage, VEC_ONLY
     uint64_t rq[NQ];
     uint32_t rl;
     double reqn[REQ ? CPL : 1];
-    StepConst kn;
     __device__ __forceinline__ void issue_step_inputs(const float *act, int64_t E, int t, int vec_io, const Params &p,
                                                       const DeviceState &s, int lane) {
         static_assert(PK, "the day kernel steps packed days");
         const size_t plane = (size_t)t * NC * (size_t)E;
         const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;   // t + 1, as issue()
-#pragma unroll
-        for (int i = 0; i < CST_COUNT; ++i) kn.v[i] = step_constant(s.tables, t, i);
-        act_tile.issue(act + e0 * p.act_dim, nw * p.act_dim, vec_io != 0, lane);
+        day_tile.issue(act + e0 * p.act_dim, nw * p.act_dim, vec_io != 0, lane);
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
             rq[q] = bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)(4 * q) * (uint32_t)E * 2u);
@@ -301,7 +300,11 @@ struct WideGroup {
                     // chargers in order: charger j waits only for its own loads.  A/B of scheduling groups
                     // (profiles/r03_ab_wide_sched_groups.txt): config 5 22.6-22.7 us with one or two chargers
                     // per group, 22.8 with five, 27.1 with no barrier in a lane's 25 chargers; the headline
-                    // within noise
+                    // within noise.  The barrier and the in-order walk answer the step kernel's load arrival; the
+                    // day kernel (KEEP) has every charger's inputs in registers before the loop and could overlap
+                    // the five chains.  Measured there, with the header and the BESS step in the same block and
+                    // every choice a select: 114.9-115.2 us per day against 114.5-114.6 (240 VGPRs), so it keeps
+                    // this form: its step was not waiting on these chains (profiles/day_kernel_chain_ab.txt)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -394,9 +397,18 @@ struct WideGroup {
                 wave_mem_fence();
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) issue_soc(j, E, s);
+                // landed here, on the rare path: the fast path writes the same registers, and a load the compiler
+                // sees pending on any way to there makes its wavefronts wait for all they have in flight
+                wave_vmem_drain();
             }
         }
         SNG_WSTAMP(2);
+        // The day kernel (KEEP) issued the next step's loads before this step, and the step's stores start here.
+        // Those loads are drained now, ahead of the stores and outside every branch: they have had the header,
+        // the BESS step and the chargers to land.  Left to their first use at the top of the next step they
+        // wait there for this step's stores too (wave_vmem_drain, sng_dev_util.h; day_wide_kernel drains the
+        // first step's before its loop), which was 1.8 of the step's 4.1 us (profiles/day_kernel_chain_ab.txt)
+        if constexpr (KEEP) wave_vmem_drain();
         if (live && leader) {
             pen_v += (t == 0) ? pen0_l : 0.0;   // python index -1 slot; every per-charger term is 0 at t = 0
             env_tail<false, true, KEEP>(p, s, info, e0, (uint32_t)le, el1, el8, t, ratio, p.bess ? bess_l : 0.0,
