@@ -323,15 +323,30 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
  * host-RNG / injected days and replayed days are stepped with different encodings (sng_layout.h:
  * packed records, requested-SoC stream, cleared Requested_SOC, day-counter ownership), so launching a
  * steps-only graph over a day of another encoding than at capture, or after t = 0, fails with
- * SNG_ERR_STATE. */
+ * SNG_ERR_STATE.
+ * A reset graph of two or more days without SNG_GRAPH_TRAJECTORY, at the stations whose day measured shorter that
+ * way (csrc/sng_step_plan.h, reset_overlapped: 10 chargers without V2X or stochastic profiles), generates day
+ * d + 1 while day d is stepped: the generator nodes sit on a parallel branch
+ * of the graph and write every other day into a second set of day buffers the handle allocates for this (about
+ * the size of one packed day).  The days drawn, the outputs, the day returns and the state the graph leaves --
+ * the last day is always in the handle's own buffers -- are bit for bit those of the serial chain; only the
+ * t = 0 observation of each day, which step 0 overwrites in the same block, is never written.  Parallel branches
+ * need the process's default of 4 hardware queues.  SNG_GRAPH_SERIAL_RESET captures the serial chain (every
+ * day's generator, then its steps); SNG_GRAPH_OVERLAPPED_RESET overlaps at every station whose device reset is
+ * one launch (about 60 chargers), also where the serial chain measured no slower and is the default (the lean
+ * stations, 50 chargers).  The serial flag wins over it, and so do one day and a kept trajectory. */
 #define SNG_GRAPH_RESET 1        /* start every day with a device-RNG reset */
 #define SNG_GRAPH_STEP_NODES 2   /* one graph node per step even where a day kernel exists (A/B, tests) */
 #define SNG_GRAPH_TRAJECTORY 4   /* obs / reward / done hold every step of every day (shapes above) */
+#define SNG_GRAPH_SERIAL_RESET 8 /* no generator beside the previous day's steps (A/B, tests) */
+#define SNG_GRAPH_OVERLAPPED_RESET 16 /* ... and beside them at every station whose reset is one launch (A/B, tests) */
 int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                      const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out);
 int sng_graph_launch(SngGraph *graph, void *stream);
 /* Graph nodes that step one day: 1 with the day kernel, else T (-1 for NULL). */
 int sng_graph_step_nodes(const SngGraph *graph);
+/* 1: the graph generates day d + 1 beside day d's steps (above); 0: the serial chain (-1 for NULL). */
+int sng_graph_reset_overlapped(const SngGraph *graph);
 /* Kernel-time probe: runs `days` device-RNG days eagerly (as the graph does) and returns the
  * device time (ms) of every step kernel, ms[days*T], from HIP start/stop events attached to
  * each dispatch (hipExtLaunchKernel: the dispatch's own begin/end timestamps), and, when reset_ms

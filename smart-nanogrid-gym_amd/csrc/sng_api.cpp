@@ -28,6 +28,40 @@ int ensure_req(SngEnv *env) {
     return SNG_OK;
 }
 
+int ensure_shadow(SngEnv *env, DeviceState *out) {
+    DaySlot &sh = env->shadow;
+    const Params &p = env->p;
+    const size_t E = (size_t)env->E;
+    // a packed day's T + 1 record planes (sng_layout.h), and a spare one: the kernels address the planes through
+    // unbounded buffer descriptors, idle lanes of a last wavefront included
+    const size_t rec_bytes = (size_t)(p.T + 2) * (size_t)p.n * ((E + 255) / 256 * 256) * sizeof(uint16_t);
+    struct {
+        void **ptr;
+        size_t bytes;
+    } const arrays[] = {
+        {(void **)&sh.soc, E * p.n * sizeof(double)},
+        {(void **)&sh.ratio, E * sizeof(double)},
+        {(void **)&sh.pen0, E * sizeof(double)},
+        {(void **)&sh.aux, rec_bytes},
+        {(void **)&sh.day_return, E * sizeof(double)},
+        {(void **)&sh.req, env->ds.req ? env->timeline() * sizeof(double) : 0},
+        {(void **)&sh.prof_key, p.noise ? 2 * E * sizeof(uint32_t) : 0},
+    };
+    for (const auto &a : arrays) {
+        if (*a.ptr || !a.bytes) continue;
+        HIP_TRY(env, hipMalloc(a.ptr, a.bytes));
+        HIP_TRY(env, hipMemset(*a.ptr, 0, a.bytes));
+    }
+    *out = env->ds;
+    out->soc = sh.soc;
+    out->ratio = sh.ratio;
+    out->pen0 = sh.pen0;
+    out->aux = sh.aux;
+    out->req = sh.req;
+    out->prof_key = sh.prof_key;   // (`word`: a packed day has no word plane)
+    return SNG_OK;
+}
+
 int await_prepare(SngEnv *env, hipStream_t st) {
     if (env->prep_launched) HIP_TRY(env, hipStreamWaitEvent(st, env->prep_done, 0));
     return SNG_OK;
@@ -374,7 +408,9 @@ void sng_destroy(SngEnv *env) {
     }
     DeviceState &ds = env->ds;
     void *dev[] = {ds.soc, ds.bess, ds.bess0, ds.ratio, ds.pen0, ds.word, ds.aux, ds.req, ds.flags, ds.prof_key,
-                   ds.episode, env->d_tables, env->rs.mt, env->rs.pos, env->ps.mt, env->ps.pos};
+                   ds.episode, env->d_tables, env->rs.mt, env->rs.pos, env->ps.mt, env->ps.pos,
+                   env->shadow.soc, env->shadow.ratio, env->shadow.pen0, env->shadow.aux, env->shadow.req,
+                   env->shadow.prof_key, env->shadow.day_return};
     for (void *x : dev)
         if (x) (void)hipFree(x);
     void *host[] = {env->h_word, env->h_aux, env->h_req, env->h_ratio, env->h_pen0};

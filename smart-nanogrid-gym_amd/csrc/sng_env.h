@@ -14,6 +14,19 @@
 #include "sng_layout.h"
 #include "sng_state_format.h"
 
+// The second day slot of an overlapped reset graph (sng_graph.cpp; sng_step_plan.h reset_overlapped): buffers of
+// its own for everything the device generator writes for a day -- the packed record timeline (`aux`, sized for a
+// packed day), the SoC seed the steps then run on, the PV ratio, the t = 0 penalty, the profile keys (where
+// Params::noise) and the requested-SoC plane (where enabled) -- and a day-return row [E] for graphs created
+// without day_returns.  Everything else of a DeviceState (bess, bess0, flags, the day counter, the tables) is
+// shared with the handle's own.  Allocated by the first graph that needs it, freed with the handle; never
+// exported, checkpointed or loaded: a graph's last day is always in the handle's own buffers.
+struct DaySlot {
+    double *soc = nullptr, *ratio = nullptr, *pen0 = nullptr, *aux = nullptr, *req = nullptr;
+    uint32_t *prof_key = nullptr;
+    double *day_return = nullptr;
+};
+
 struct SngEnv {
     SngConfig cfg{};
     sng::Params p{};
@@ -33,6 +46,7 @@ struct SngEnv {
     bool gen_loaded = false;          // its timeline is still the loaded one (no injected day since)
     uint64_t replays = 0;             // device-RNG replays so far: the replay ratio stream's counter
     sng::DeviceState ds{};
+    DaySlot shadow{};                 // ensure_shadow
     sng::Tables *d_tables = nullptr;
     // host staging (pinned) for days built on the CPU
     uint32_t *h_word = nullptr;
@@ -66,6 +80,7 @@ struct SngGraph {
     SngEnv *env = nullptr;
     bool with_reset = false;
     bool day_kernel = false;   // each day's steps are one day-kernel node (sng_step_day.h), not T step nodes
+    bool overlapped = false;   // day d + 1 is generated beside day d's steps (sng_step_plan.h reset_overlapped)
     sng::DayKey key{};   // the loaded-day encoding the graph's steps were captured for
     // the stream keys baked into the captured kernels' arguments: the device days a reset graph draws
     // and the PV-ratio / profile streams are those of this seed and env offset
@@ -167,6 +182,8 @@ inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 // Defined in sng_api.cpp, called from sng_state.cpp and sng_graph.cpp too.
 // the requested-SoC plane, on first use
 int ensure_req(SngEnv *env);
+// the second day slot, on first use; `out`: the handle's DeviceState with the slot's buffers in place of its own
+int ensure_shadow(SngEnv *env, DeviceState *out);
 // Orders `st` after the side stream's preparation of the streams (sng_reset), before st touches them.
 int await_prepare(SngEnv *env, hipStream_t st);
 // one stream set's device blocks ([E][2][624] words and the positions), on first use

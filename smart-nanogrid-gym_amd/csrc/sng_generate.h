@@ -283,6 +283,11 @@ __device__ __forceinline__ VehicleDraw draw_vehicle(const Params &p, GenStream &
 constexpr int kObsParts = kGenBlock / kWave;       // wavefronts per observation block (threads per env)
 constexpr int kObsEnvs = kGenBlock / kObsParts;    // envs per observation block
 constexpr int kObsBlocks = kGenBlock / kObsEnvs;   // observation blocks per 256 envs
+static_assert(kObsEnvs == kGenObsEnvs, "generator_fused (sng_step_plan.h) sizes the observation tile");
+// obs == nullptr (the overlapped reset of a captured graph, sng_graph.cpp): the day's values are written -- ratio,
+// pen0, the profile keys, the SoC seed, the zeroed return -- and the row is not: step 0 overwrites it before a
+// caller could read it, and neither the observation buffer nor the BESS state is touched, which the day being
+// stepped beside this generator owns.
 __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4,
                                              int i10, int i1, uint64_t day, float *__restrict__ obs,
                                              double *__restrict__ ep_return, int vec_io, float *lds, int q) {
@@ -312,8 +317,10 @@ __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState 
                     if (p.price_noise != 0.0) fpr[k] = profile_factor(env_seed, kDomainPrice, day, k, p.price_noise);
                 }
             }
-            write_obs_header(o_row, p, s.tables->irr_norm, s.tables->price_norm, ratio, fpv, fpr);
-            if (p.bess) o_row[O - 1] = (float)s.bess[e];
+            if (obs) {
+                write_obs_header(o_row, p, s.tables->irr_norm, s.tables->price_norm, ratio, fpv, fpr);
+                if (p.bess) o_row[O - 1] = (float)s.bess[e];
+            }
             if (ep_return) ep_return[e] = 0.0;
         }
         const int k = p.pv ? 8 : 4;
@@ -329,8 +336,10 @@ __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState 
                 const VehicleDraw d = draw_vehicle(p, rng, 0, i4, i10, i1);
                 const bool occ0 = d.ta == 0;   // t = 0 < T always, and dep >= 4/dt > 0
                 soc0[i] = occ0 ? d.soc : 0.0;
-                o_row[k + c] = (float)soc0[i];
-                o_row[k + n + c] = departure_obs(pack_word(occ0, occ0, false, 0u, occ0 ? (uint32_t)d.dep : 0u));
+                if (obs) {
+                    o_row[k + c] = (float)soc0[i];
+                    o_row[k + n + c] = departure_obs(pack_word(occ0, occ0, false, 0u, occ0 ? (uint32_t)d.dep : 0u));
+                }
             }
             const SocOff so = soc_off(c0, n, E, el8);
             if (c0 + 1 < n)
@@ -339,6 +348,7 @@ __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState 
                 bst<kNT>(s.soc, so.v, soc0[0], so.s);
         }
     }
+    if (!obs) return;   // the whole grid alike
     __syncthreads();
     copy_out<kGenBlock>(obs + e0 * O, lds, nblk * O, vec_io != 0, tid);
 }
@@ -351,7 +361,9 @@ __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState 
 //  2. the dense timeline, step by step, from the vehicle list kept in LDS.
 // Grid (E / 256, rows + 4): blocks y < gen_rows(N) the timeline of charger quad y / 4, the last 4 rows the
 // t = 0 observation (observe_day0).  The day counter is read here and advanced by the day's first step
-// (step_kernel, t = 0), so no block of this grid waits on another.
+// (step_kernel, t = 0), so no block of this grid waits on another.  day_delta: the day drawn is the counter's
+// plus this -- 0 but in an overlapped reset graph, whose generators all run before anything advances the counter
+// (sng_step_plan.h day_shape).
 // The timeline records leave as streaming (nontemporal) stores: reset 24.5-24.7 -> 22.5-22.7 us per day
 // at 65,536 x 10 (A/B, one box), the steps' code and state staying in L2.  Diagnostic builds
 // (round 2's -DSNG_GX_* builds, in commits before 8be1f55) split the reset's time: without the t = 0 observation blocks 24.3-24.9 us
@@ -376,7 +388,8 @@ constexpr uint32_t kVehRecMask = 0x3fff8u;         // capacity (3-9) and departu
 template <int TT, bool REQ>
 __global__ __launch_bounds__(kGenBlock) void generate_kernel(Params p, DeviceState s, uint64_t seed, int64_t E,
                                                              int i4, int i10, int i1, float *__restrict__ obs,
-                                                             double *__restrict__ ep_return, int vec_io) {
+                                                             double *__restrict__ ep_return, int vec_io,
+                                                             int day_delta) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     uint32_t *s_veh = reinterpret_cast<uint32_t *>(lds);                      // [V][BLOCK] arr | cap<<8 | dep<<16
     uint32_t *s_car = s_veh + kDaySlots * kGenBlock;                           // [V][BLOCK] arrival SoC carry bits
@@ -389,7 +402,7 @@ __global__ __launch_bounds__(kGenBlock) void generate_kernel(Params p, DeviceSta
     // waves instead of delaying them: reset 16.0-16.3 -> 15.5-15.6 us (A/B three times on one box, same days,
     // profiles/r06_ab_generator_obs_order.txt; round 3's kernel had measured the opposite order 0.6 % better)
     const int u = (int)blockIdx.y;
-    const uint64_t day = *s.episode;
+    const uint64_t day = *s.episode + (uint64_t)day_delta;
     if (u >= gen_rows(p.n)) {
         observe_day0(p, s, seed, E, i4, i10, i1, day, obs, ep_return, vec_io, lds, u - gen_rows(p.n));
         return;

@@ -41,37 +41,107 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     // a day's T steps as one day-kernel node where the plan has one (sng_step_plan.h day_kernel_of), else -- or
     // with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
     g->day_kernel = !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    // Overlapped (sng_step_plan.h reset_overlapped, day_shape): the generators are captured on a second stream, day
+    // d + 1's into the day slot that day d does not use, so it runs beside day d's steps.  The edges are gen(d) ->
+    // day(d), day(d - 1) -> day(d) and day(d - 1) -> gen(d + 1) (the slot is free again); the generators follow
+    // one another on their stream, and the node that advances the day counter for all days but the last follows
+    // the last of them, when no generator reads the counter any more.
+    // Both kernels become ready at the same join, and a generator that fills the CUs first delays the day's steps by
+    // more than it hides: its workgroups ask for generator_lds of dynamic LDS so that fewer of them fit a CU.
+    size_t generator_lds = 0;
+    g->overlapped = with_reset && reset_graph_overlapped(p, ip, days, traj, (flags & SNG_GRAPH_SERIAL_RESET) != 0,
+                                                         (flags & SNG_GRAPH_OVERLAPPED_RESET) != 0, &generator_lds) != 0;
+    DeviceState slots[2] = {env->ds, env->ds};
+    hipStream_t gs = nullptr;                      // the generators' stream
+    std::vector<hipEvent_t> generated, stepped;   // day d's generator / steps are captured
+    hipError_t e = hipSuccess;
+    if (g->overlapped) {
+        if (int rc = ensure_shadow(env, &slots[1])) {
+            (void)hipStreamDestroy(cs);
+            delete g;
+            return rc;
+        }
+        generated.assign((size_t)days, nullptr);
+        stepped.assign((size_t)days, nullptr);
+        e = hipStreamCreateWithFlags(&gs, hipStreamNonBlocking);
+        for (int d = 0; d < days; ++d) {
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&generated[(size_t)d], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&stepped[(size_t)d], hipEventDisableTiming);
+        }
+    }
+    auto row = [&](int d, const DayShape &sh) {   // day d's returns (the generator zeroes the row, every step adds)
+        InfoPtrs ipd = ip;
+        if (day_returns) ipd.episode_return = day_returns + (size_t)d * E;   // into row d
+        else if (sh.slot && ip.episode_return) ipd.episode_return = env->shadow.day_return;
+        return ipd;
+    };
+    // an overlapped graph's generator of day d, on `gs`
+    auto capture_generator = [&](int d) {
+        const DayShape sh = day_shape(true, days, d);
+        if (d >= 2) e = hipStreamWaitEvent(gs, stepped[(size_t)d - 2], 0);
+        if (e == hipSuccess)
+            e = launch_generate(p, slots[sh.slot], env->seed, E, sp.i4, sp.i10, sp.i1, nullptr, row(d, sh).episode_return,
+                                0, gs, nullptr, nullptr, sh.day_delta, generator_lds);
+        if (e == hipSuccess) e = hipEventRecord(generated[(size_t)d], gs);
+        if (e == hipSuccess && sh.bump_node) e = launch_bump_day(env->ds, gs, (uint64_t)sh.bump_node);
+    };
+    if (e == hipSuccess) e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    const bool capturing = e == hipSuccess;
+    if (g->overlapped && e == hipSuccess) {   // fork
+        e = hipEventRecord(stepped[0], cs);
+        if (e == hipSuccess) e = hipStreamWaitEvent(gs, stepped[0], 0);
+        if (e == hipSuccess) capture_generator(0);
+    }
     for (int d = 0; e == hipSuccess && d < days; ++d) {
-        InfoPtrs ipd = ip;   // day d's returns into row d (observe0 zeroes it, every step adds)
-        if (day_returns) ipd.episode_return = day_returns + (size_t)d * E;
+        const DayShape sh = day_shape(g->overlapped, days, d);
+        const InfoPtrs ipd = row(d, sh);
+        const DeviceState &ds = slots[sh.slot];
+        Params pd = p;
+        if (g->overlapped) pd.bump_day = sh.bump_day;
         // day d's blocks: the reset's observation, then step 0's outputs
         float *obs0 = obs + (traj ? (size_t)d * (size_t)(p.T + 1) * obs_block : 0);
         float *obs_d = obs0 + obs_step;
         double *reward_d = reward + (traj ? (size_t)d * (size_t)p.T * (size_t)E : 0);
         uint8_t *done_d = done + (traj ? (size_t)d * (size_t)p.T * (size_t)E : 0);
-        if (with_reset) {
-            e = launch_generate(p, env->ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs0, ipd.episode_return,
+        if (g->overlapped) {
+            e = hipStreamWaitEvent(cs, generated[(size_t)d], 0);
+        } else if (with_reset) {
+            e = launch_generate(p, ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs0, ipd.episode_return,
                                 (vec && aligned16(obs0)) ? 1 : 0, cs);
         }
         if (g->day_kernel) {
             if (e == hipSuccess)
-                e = launch_day(p, env->ds, ipd, actions, obs_d, reward_d, done_d, E, 0, p.T,
+                e = launch_day(pd, ds, ipd, actions, obs_d, reward_d, done_d, E, 0, p.T,
                                (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step);
-            continue;
+        } else {
+            for (int t = 0; e == hipSuccess && t < p.T; ++t) {
+                float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
+                e = launch_step(pd, ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs_t,
+                                reward_d + (size_t)t * (size_t)out_step, done_d + (size_t)t * (size_t)out_step, E, t,
+                                (vec && aligned16(obs_t)) ? 1 : 0, cs);
+            }
         }
-        for (int t = 0; e == hipSuccess && t < p.T; ++t) {
-            float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
-            e = launch_step(p, env->ds, ipd, env->host_tab, actions + (size_t)t * E * A, obs_t,
-                            reward_d + (size_t)t * (size_t)out_step, done_d + (size_t)t * (size_t)out_step, E, t,
-                            (vec && aligned16(obs_t)) ? 1 : 0, cs);
+        if (g->overlapped) {
+            if (e == hipSuccess) e = hipEventRecord(stepped[(size_t)d], cs);
+            // behind day d's steps in capture order (ahead of them measured the same, profiles/overlapped_reset_ab.txt)
+            if (e == hipSuccess && d + 1 < days) capture_generator(d + 1);
         }
     }
+    if (g->overlapped && capturing) {   // join: the bump node is the generators' stream's last
+        hipError_t ej = hipEventRecord(generated[0], gs);
+        if (ej == hipSuccess) ej = hipStreamWaitEvent(cs, generated[0], 0);
+        if (e == hipSuccess) e = ej;
+    }
     hipGraph_t graph = nullptr;
-    hipError_t e2 = hipStreamEndCapture(cs, &graph);
+    hipError_t e2 = capturing ? hipStreamEndCapture(cs, &graph) : hipSuccess;
     if (e == hipSuccess) e = e2;
     if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
     (void)hipStreamDestroy(cs);
+    if (gs) (void)hipStreamDestroy(gs);
+    for (hipEvent_t x : generated)
+        if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : stepped)
+        if (x) (void)hipEventDestroy(x);
     if (e != hipSuccess) {
         if (graph) (void)hipGraphDestroy(graph);
         delete g;
@@ -112,6 +182,11 @@ int sng_graph_launch(SngGraph *g, void *stream) {
 int sng_graph_step_nodes(const SngGraph *g) {
     if (!g) return -1;
     return g->day_kernel ? 1 : g->env->p.T;
+}
+
+int sng_graph_reset_overlapped(const SngGraph *g) {
+    if (!g) return -1;
+    return g->overlapped ? 1 : 0;
 }
 
 void sng_graph_destroy(SngGraph *g) {

@@ -228,6 +228,14 @@ int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory)
     return day_kernel_of(step_plan(p, info_diag(info)), trajectory) != DAY_NONE ? 1 : 0;
 }
 
+int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
+                           size_t *generator_lds) {
+    const StepPlan pl = step_plan(p, info_diag(info));
+    if (!reset_overlapped(pl, p, days, trajectory, serial, force)) return 0;
+    if (generator_lds) *generator_lds = overlapped_generator_lds(pl);
+    return 1;
+}
+
 hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
                       double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
                       int64_t obs_step, int64_t out_step) {
@@ -280,24 +288,28 @@ hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, do
 // while its [256][obs_dim] LDS tile stays small next to the vehicle lists (N <= 16: at most 42 KB,
 // a few generator workgroups per CU still fit); wider stations keep profile_kernel and
 // observe0_kernel as separate launches behind the generator.
+// day_delta != 0 or obs == nullptr: an overlapped reset graph's generator (sng_step_plan.h reset_overlapped), the
+// one-launch form only.
 hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4, int i10, int i1,
                            float *obs, double *ep_return, int vec_io, hipStream_t stream, hipEvent_t ev_start,
-                           hipEvent_t ev_stop) {
+                           hipEvent_t ev_stop, int day_delta, size_t min_lds) {
     const size_t veh = generate_lds_bytes(p.req_enabled != 0), tile = (size_t)round4(kObsEnvs * p.obs_dim) * 4;
-    const bool fused = tile <= 32 * 1024;   // up to 60 chargers (config 5's 50: 27.9 KB)
+    const bool fused = generator_fused(p);   // up to 60 chargers (config 5's 50: 27.9 KB)
+    if (!fused && (day_delta != 0 || !obs)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((E + kGenBlock - 1) / kGenBlock), (unsigned)(gen_rows(p.n) + (fused ? kObsBlocks : 0))),
         block(kGenBlock);
-    const size_t lds = (fused && tile > veh) ? tile : veh;
+    size_t lds = (fused && obs && tile > veh) ? tile : veh;   // no row, no tile
+    if (min_lds > lds) lds = min_lds;   // fewer workgroups per CU (overlapped_generator_lds)
     const bool req = p.req_enabled != 0;
     auto kern = p.T == 24 ? (req ? generate_kernel<24, true> : generate_kernel<24, false>)
                 : (p.T == 96 && !req) ? generate_kernel<96, false>   // config 5's 15-minute day
                 : (req ? generate_kernel<0, true> : generate_kernel<0, false>);
     if (fused && ev_start && ev_stop)   // the one-launch reset, timed by its own dispatch timestamps
         return launch_kernel(kern, grid, block, lds, stream, ev_start, ev_stop, p, s, seed, E, i4, i10, i1, obs,
-                             ep_return, vec_io);
+                             ep_return, vec_io, day_delta);
     if (ev_start) (void)hipEventRecord(ev_start, stream);
     hipError_t e = launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, p, s, seed, E, i4, i10, i1, obs,
-                                 ep_return, vec_io);
+                                 ep_return, vec_io, day_delta);
     if (!fused) {
         if (e == hipSuccess) e = launch_profiles(p, s, E, stream);
         // the PV ratio and pen0 of the day, from the streams, as the fused t = 0 blocks do
@@ -378,10 +390,14 @@ hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStream
     return hipGetLastError();
 }
 
-__global__ void bump_day_kernel(DeviceState s) { *s.episode += 1; }
+// Atomic, as the first step's own advance is (bump_day_counter): in an overlapped reset graph the bump node
+// behind the last generator and the last day's first step are not ordered, and nothing reads the counter then.
+__global__ void bump_day_kernel(DeviceState s, uint64_t amount) {
+    __hip_atomic_fetch_add(s.episode, amount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
-hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream) {
-    hipLaunchKernelGGL(bump_day_kernel, dim3(1), dim3(1), 0, stream, s);
+hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t amount) {
+    hipLaunchKernelGGL(bump_day_kernel, dim3(1), dim3(1), 0, stream, s, amount);
     return hipGetLastError();
 }
 

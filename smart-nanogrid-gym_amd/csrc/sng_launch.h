@@ -27,9 +27,14 @@ hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, do
                            int py = 0);
 hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4, int i10, int i1,
                            float *obs, double *ep_return, int vec_io, hipStream_t stream,
-                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int day_delta = 0,
+                           size_t min_lds = 0);
+// Whether a reset graph of `days` days over this plan is captured overlapped (sng_step_plan.h reset_overlapped),
+// and then the dynamic LDS its generators ask for at least (overlapped_generator_lds).
+int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
+                           size_t *generator_lds);
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
-hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream);
+hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t amount = 1);
 hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,
                              hipEvent_t b);
 hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipStream_t stream);

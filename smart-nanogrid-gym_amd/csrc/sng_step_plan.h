@@ -103,6 +103,54 @@ inline DayFamily day_kernel_of(const StepPlan &pl, bool trajectory) {
     if (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10 && !trajectory) return DAY_WIDE;
     return DAY_NONE;
 }
+// A device-RNG reset is one launch -- the t = 0 observation as extra blocks of the generator's grid -- while the
+// observation blocks' [kGenObsEnvs][obs_dim] LDS tile stays small next to the vehicle lists (32 KB: up to 60
+// chargers); wider stations run profile_kernel and observe0_kernel behind the generator (launch_generate).
+constexpr int kGenObsEnvs = 64;
+inline bool generator_fused(const Params &p) { return (size_t)((kGenObsEnvs * p.obs_dim + 3) & ~3) * 4 <= 32 * 1024; }
+
+// The shape of a captured reset graph (sng_graph_create with SNG_GRAPH_RESET).  Serial: every day's generator, then
+// its steps, in one chain.  Overlapped: day d + 1 is generated into a second day slot while day d is stepped.
+// Decided here and nowhere else, for a plan and a graph: at least two days, no kept trajectory (the generator
+// would have to write every day's t = 0 observation; without one, step 0 overwrites that row, so the overlapped
+// generator skips it), the one-launch generator, no SNG_GRAPH_SERIAL_RESET -- and a plan whose day measured
+// shorter that way (device time per day at 65,536 envs, serial -> overlapped, profiles/overlapped_reset_ab.txt),
+// whether its day is a day-kernel node or T step nodes:
+//   - the wide family's 10-charger station: 93.3 -> 87.0 us (with the requested-SoC stream 126.3 -> 123.1).
+// Not shorter, so serial unless forced (SNG_GRAPH_OVERLAPPED_RESET, `force`: A/B runs and tests):
+//   - the lean family's 8 chargers: 119.6 -> 112.6 - 117.3 us between HIP events, but bench.py's wall time 0.4 -
+//     1.2 % behind the parent's; 4 chargers 68.5 -> 70.8 us; 16 chargers 184.8 -> 240.2 us;
+//   - config 5's 50 chargers, 2.12 -> 2.15 ms: its step kernel's eight wavefronts take a CU's whole LDS, so a
+//     generator workgroup that gets in keeps a wavefront out;
+//   - every plan that was not measured.
+inline bool reset_overlapped(const StepPlan &pl, const Params &p, int days, bool trajectory, bool serial,
+                             bool force = false) {
+    const bool faster = pl.family == STEP_WIDE && pl.nc == 10;
+    return days >= 2 && !trajectory && !serial && generator_fused(p) && (faster || force);
+}
+// The dynamic LDS an overlapped graph's generator workgroups ask for at least (bytes; 0: what they need).  Beside
+// the wide family's day, which has exactly two wavefronts per SIMD to run and 40 KB of tiles per CU to place, the
+// generator at its own eight wavefronts per SIMD doubled in length and stretched the day by more than the reset
+// it hid (93.6 -> 101.6 us).  With 56 KB a workgroup, two fit a CU and leave the day's wavefronts their room:
+// 85.5 us on that box (54 - 60 KB alike; 41 KB, three a CU: 93.6; 64 KB, which leaves 32 KB: 98.2).  The lean
+// family's day is one wavefront per SIMD and was shorter beside the uncapped generator (N = 8: 114.9 us, capped
+// 117.2 - 118.3), so a forced overlap there is not capped.
+inline size_t overlapped_generator_lds(const StepPlan &pl) { return pl.family == STEP_WIDE ? 56u * 1024u : 0u; }
+// Day d of `days` in such a graph: the day slot it is generated into and stepped in (0: the handle's own
+// buffers, 1: the shadow's -- the last day is always in slot 0, so after a replay the loaded day is where every
+// other call expects it); the day index its generator draws, as an offset from the day counter at launch (the
+// overlapped generators all read the counter before anything advances it); whether the day's first step advances
+// the counter (Params::bump_day); and the amount a bump node behind the day's generator adds.  Per replay the
+// counter advances by `days` in both forms.
+struct DayShape {
+    int slot, day_delta, bump_day, bump_node;
+};
+inline DayShape day_shape(bool overlapped, int days, int d) {
+    if (!overlapped) return {0, 0, 1, 0};
+    const bool last = d == days - 1;
+    return {(days - 1 - d) & 1, d, last ? 1 : 0, last ? days - 1 : 0};
+}
+
 // The name rocprofv3 reports for a plan's day kernel; an empty string where it has none.
 inline int day_plan_name(const StepPlan &pl, bool trajectory, char *buf, int len) {
     auto b = [](bool v) { return v ? "true" : "false"; };

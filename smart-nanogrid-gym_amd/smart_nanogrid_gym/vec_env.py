@@ -927,12 +927,16 @@ class EpisodeGraph:
     graph copies venv.obs_d there at every launch), reward_traj[d, t] and done_traj[d, t] are step t's, and
     obs_traj[d, t + 1] is the observation step t returned."""
 
-    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False, trajectory=False):
+    def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False, trajectory=False,
+                 serial_reset=False, overlapped_reset=False):
         """days > 1 captures that many consecutive days (each with its reset) in one graph,
         which amortises the graph launch.  day_returns: optional device tensor [days, E] f64;
         day d's returns accumulate into row d (instead of venv.return_d).  A seed left by seed() takes effect
         here for a graph of whole days (with_reset); a steps-only graph steps the loaded day, so it is refused
-        while a seed waits for the next reset."""
+        while a seed waits for the next reset.  serial_reset=True captures every day's reset ahead of its steps
+        even where the graph would generate the next day beside them (sng.h SNG_GRAPH_SERIAL_RESET; the same
+        results; for A/B and tests); overlapped_reset=True does so at every station it can
+        (SNG_GRAPH_OVERLAPPED_RESET), also where the serial chain is the default."""
         if with_reset:
             venv._apply_pending_seed()
         elif venv._seeds[0] is not None:
@@ -965,7 +969,9 @@ class EpisodeGraph:
                                          ctypes.c_void_p(done.data_ptr()), ctypes.byref(venv._info),
                                          (_native.GRAPH_RESET if with_reset else 0)
                                          | (_native.GRAPH_STEP_NODES if step_nodes else 0)
-                                         | (_native.GRAPH_TRAJECTORY if self.trajectory else 0),
+                                         | (_native.GRAPH_TRAJECTORY if self.trajectory else 0)
+                                         | (_native.GRAPH_SERIAL_RESET if serial_reset else 0)
+                                         | (_native.GRAPH_OVERLAPPED_RESET if overlapped_reset else 0),
                                          self.days, dr, ctypes.byref(g)), venv._h)
         self._g = g
 
@@ -973,6 +979,11 @@ class EpisodeGraph:
     def step_nodes_per_day(self):
         """Graph nodes that step one day: 1 with the day kernel, else T."""
         return int(lib().sng_graph_step_nodes(self._g))
+
+    @property
+    def reset_overlapped(self):
+        """Whether the graph generates day d + 1 while day d is stepped (include/sng.h, sng_graph_create)."""
+        return bool(lib().sng_graph_reset_overlapped(self._g))
 
     def launch(self, stream=None):
         s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)
