@@ -340,10 +340,11 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
 #define SNG_GRAPH_TRAJECTORY 4   /* obs / reward / done hold every step of every day (shapes above) */
 #define SNG_GRAPH_SERIAL_RESET 8 /* no generator beside the previous day's steps (A/B, tests) */
 #define SNG_GRAPH_OVERLAPPED_RESET 16 /* ... and beside them at every station whose reset is one launch (A/B, tests) */
+#define SNG_GRAPH_POLICY_FUSED 32 /* sng_graph_create_policy: the fused day wherever it is compiled (A/B, tests) */
 int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                      const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out);
 int sng_graph_launch(SngGraph *graph, void *stream);
-/* Graph nodes that step one day: 1 with the day kernel, else T (-1 for NULL). */
+/* Graph nodes that step one day: 1 with the day kernel, else T; a policy graph's node form has 2T (-1 for NULL). */
 int sng_graph_step_nodes(const SngGraph *graph);
 /* 1: the graph generates day d + 1 beside day d's steps (above); 0: the serial chain (-1 for NULL). */
 int sng_graph_reset_overlapped(const SngGraph *graph);
@@ -356,6 +357,71 @@ int sng_graph_reset_overlapped(const SngGraph *graph);
 int sng_time_step_kernels(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                           const SngInfo *info, int32_t days, float *ms, float *reset_ms, void *stream);
 void sng_graph_destroy(SngGraph *graph);
+
+/* ---------------------------------------------------------------------------------------------
+ * Policy in the loop: the actor of the reference's own workload, PPO("MlpPolicy", env)
+ * (solvers/RL/ppo_train.py:92), evaluated on the device between steps, so a day whose step t + 1 actions depend on
+ * step t's observation runs without a torch kernel in between.
+ *
+ * The actor's arithmetic is one contract, the same on the host (sng_policy_host_actions) and on the device.  x is
+ * an env's observation row; weights are in torch's nn.Linear layout [out][in]; every layer's output j is the
+ * k-ordered float32 fmaf chain started from the bias:
+ *     h = b[j];  for k = 0 .. K-1:  h = fmaf(in[k], W[j][k], h)
+ * Two hidden layers of 64 units with tanh or relu (relu(h) = h > 0 ? h : 0); the output layer has no activation and
+ * gives the mean; a = mean + noise (one float32 add) when a noise block is given, else the mean; `a` is what is
+ * stored as the step's action, and the env is stepped with min(max(a, low), high) when the spec has clip bounds,
+ * else with a.  With relu the device reproduces the host bit for bit; with tanh up to the device's tanhf.
+ * Another hidden width returns SNG_ERR_UNSUPPORTED; non-finite weights are refused at upload
+ * (SNG_ERR_INVALID_ARGUMENT); what non-finite observations give is unspecified. */
+typedef struct SngMlpSpec {
+    int32_t obs_dim, act_dim;
+    int32_t hidden;                 /* 64 */
+    int32_t activation;             /* 0 tanh, 1 relu */
+    const float *clip_low, *clip_high;   /* host [act_dim]; both NULL = no clip */
+} SngMlpSpec;
+typedef struct SngMlpWeights {      /* host memory, [out][in] and [out] */
+    const float *w1, *b1;           /* [64][obs_dim], [64] */
+    const float *w2, *b2;           /* [64][64], [64] */
+    const float *w3, *b3;           /* [act_dim][64], [act_dim] */
+} SngMlpWeights;
+typedef struct SngPolicy SngPolicy;
+
+/* An actor for `env`: spec->obs_dim and act_dim must be the env's.  Its weights are zero until
+ * sng_policy_set_weights.  A policy must outlive the graphs created with it and be destroyed before its env. */
+int sng_policy_create(SngEnv *env, const SngMlpSpec *spec, SngPolicy **out);
+/* Upload into the policy's device image, asynchronously on `stream`.  Captured graphs read that image, so new
+ * weights between two launches change the next launch without a recapture (one PPO iteration). */
+int sng_policy_set_weights(SngPolicy *policy, const SngMlpWeights *weights, void *stream);
+/* One launch (policy_kernel) over the env's num_envs rows: obs [num_envs][obs_dim], noise [num_envs][act_dim] or
+ * NULL, actions [num_envs][act_dim] (a), env_actions [num_envs][act_dim] or NULL (what sng_step is to be given);
+ * device pointers.  Works at every station.  Asynchronous on `stream`. */
+int sng_policy_actions(SngPolicy *policy, const float *obs, const float *noise, float *actions, float *env_actions,
+                       void *stream);
+void sng_policy_destroy(SngPolicy *policy);
+
+/* sng_graph_create with the policy in the loop: every step's actions are the actor's answer to the observation the
+ * step before it (or the day's reset) wrote.  noise holds T consecutive [num_envs][act_dim] blocks reused every
+ * day, or is NULL.  flags, days, day_returns, info and obs / reward / done are sng_graph_create's, the steps-only
+ * rules (the loaded day's encoding, t = 0) included; a steps-only graph reads the day's t = 0 observation from obs
+ * (block [0][0] with SNG_GRAPH_TRAJECTORY), where the reset or the caller left it.  actions_out receives a: one block
+ * [num_envs][act_dim] that every step overwrites, or [days][T][num_envs][act_dim] with SNG_GRAPH_TRAJECTORY.
+ * The form of a day is decided per plan in csrc/sng_step_plan.h (policy_day_form).  Node form: T x (policy_kernel
+ * node, step node), the step nodes being those of sng_graph_create; sng_graph_step_nodes reports 2T.  Fused form: one
+ * node a day, day_lean_policy_kernel, the lean day kernel with the actor between its steps (one wavefront per 64
+ * envs, the observation and the actions never leave LDS between the actor and the step); sng_graph_step_nodes
+ * reports 1.  The fused form exists for the plans with a lean day kernel; it is a plan's default only where its day
+ * measured shorter than the node form's (nowhere in this build: DESIGN.md section 4.6, profiles/policy_day_ab.txt),
+ * and SNG_GRAPH_POLICY_FUSED takes it wherever it exists.  SNG_GRAPH_STEP_NODES and SngInfo diagnostics force the
+ * node form.  Both forms leave the same bytes.  Policy graphs capture the serial chain: sng_graph_reset_overlapped
+ * gives 0, whatever the reset flags. */
+int sng_graph_create_policy(SngEnv *env, SngPolicy *policy, const float *noise, float *obs, float *actions_out,
+                            double *reward, uint8_t *done, const SngInfo *info, int flags, int32_t days,
+                            double *day_returns, SngGraph **out);
+
+/* Host only: the actor's contract on the CPU (csrc/sng_policy_host.h, mlp_actor_host) over `rows` rows of host
+ * memory.  noise and env_actions may be NULL.  Validates as sng_policy_create and sng_policy_set_weights do. */
+int sng_policy_host_actions(const SngMlpSpec *spec, const SngMlpWeights *w, int64_t rows, const float *obs,
+                            const float *noise, float *actions, float *env_actions);
 
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for

@@ -76,8 +76,22 @@ struct SngEnv {
     size_t timeline() const { return (size_t)p.T * p.n * (size_t)E; }
 };
 
+// An MLP actor of a handle's envs (sng_policy.cpp): the spec, the device image the policy kernels and the graphs
+// captured with it read (sng_policy_host.h, PolicyImage), its pinned host mirror, which sng_policy_set_weights packs
+// and uploads from, and the clipped actions a captured step node reads.
+struct SngPolicy {
+    SngEnv *env = nullptr;
+    SngMlpSpec spec{};
+    std::vector<float> clip_low, clip_high;   // owned copies behind spec.clip_low / clip_high
+    sng::PolicyImage image{};
+    float *d_img = nullptr, *h_img = nullptr;
+    float *d_env_actions = nullptr;           // [E][act_dim]
+    hipEvent_t uploaded = nullptr;            // the last upload has read h_img
+};
+
 struct SngGraph {
     SngEnv *env = nullptr;
+    SngPolicy *policy = nullptr;   // sng_graph_create_policy: the actor between the steps
     bool with_reset = false;
     bool day_kernel = false;   // each day's steps are one day-kernel node (sng_step_day.h), not T step nodes
     bool overlapped = false;   // day d + 1 is generated beside day d's steps (sng_step_plan.h reset_overlapped)

@@ -6,11 +6,15 @@
 
 using namespace sng;
 
-extern "C" {
-
-int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
-                     const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out) {
+// sng_graph_create and sng_graph_create_policy.  Without a policy, `actions` holds the day's T action blocks.  With
+// one (sng_policy.cpp), every step's actions are the actor's answer to the observation before it: `noise` (T
+// blocks, may be null) takes the place of the actions stream, `actions_out` receives a, and the step nodes read the
+// policy's clipped actions.
+static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, const float *noise, float *actions_out,
+                        float *obs, double *reward, uint8_t *done, const SngInfo *info, int flags, int32_t days,
+                        double *day_returns, SngGraph **out) {
     const bool with_reset = (flags & SNG_GRAPH_RESET) != 0;
+    if (policy) actions = policy->d_env_actions;
     if (!env || !actions || !obs || !reward || !done || !out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
     if (days < 1 || (days > 1 && !with_reset))
         return fail(env, SNG_ERR_INVALID_ARGUMENT, "days must be >= 1 (more than one needs SNG_GRAPH_RESET)");
@@ -22,6 +26,7 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     HIP_TRY(env, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     SngGraph *g = new SngGraph();
     g->env = env;
+    g->policy = policy;
     // with a reset: every day a freshly generated device day (sng_reset(SNG_RNG_DEVICE)); else the loaded day
     g->with_reset = with_reset;
     g->key = with_reset ? DayKey::device_day(env->p) : DayKey::of(env->p);
@@ -40,7 +45,11 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     const int64_t obs_step = traj ? (int64_t)obs_block : 0, out_step = traj ? E : 0;
     // a day's T steps as one day-kernel node where the plan has one (sng_step_plan.h day_kernel_of), else -- or
     // with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
-    g->day_kernel = !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
+    // with a policy: one fused node where the plan has that form (sng_step_plan.h policy_day_form), else T x (policy
+    // node, step node)
+    g->day_kernel = policy ? policy_day_fused(p, ip, traj, (flags & SNG_GRAPH_STEP_NODES) != 0,
+                                              (flags & SNG_GRAPH_POLICY_FUSED) != 0) != 0
+                           : !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
     // Overlapped (sng_step_plan.h reset_overlapped, day_shape): the generators are captured on a second stream, day
     // d + 1's into the day slot that day d does not use, so it runs beside day d's steps.  The edges are gen(d) ->
     // day(d), day(d - 1) -> day(d) and day(d - 1) -> gen(d + 1) (the slot is free again); the generators follow
@@ -49,7 +58,7 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     // Both kernels become ready at the same join, and a generator that fills the CUs first delays the day's steps by
     // more than it hides: its workgroups ask for generator_lds of dynamic LDS so that fewer of them fit a CU.
     size_t generator_lds = 0;
-    g->overlapped = with_reset && reset_graph_overlapped(p, ip, days, traj, (flags & SNG_GRAPH_SERIAL_RESET) != 0,
+    g->overlapped = !policy && with_reset && reset_graph_overlapped(p, ip, days, traj, (flags & SNG_GRAPH_SERIAL_RESET) != 0,
                                                          (flags & SNG_GRAPH_OVERLAPPED_RESET) != 0, &generator_lds) != 0;
     DeviceState slots[2] = {env->ds, env->ds};
     hipStream_t gs = nullptr;                      // the generators' stream
@@ -109,7 +118,25 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
             e = launch_generate(p, ds, env->seed, E, sp.i4, sp.i10, sp.i1, obs0, ipd.episode_return,
                                 (vec && aligned16(obs0)) ? 1 : 0, cs);
         }
-        if (g->day_kernel) {
+        if (policy) {
+            // step t answers the observation in block t of the day (the reset's, then step t - 1's)
+            const size_t act_block = (size_t)E * (size_t)A;
+            float *a_d = actions_out + (traj ? (size_t)d * (size_t)p.T * act_block : 0);
+            if (e == hipSuccess && g->day_kernel)
+                e = launch_policy_day(pd, ds, ipd, policy->d_img, policy->image, noise, obs0, obs_d, a_d, reward_d, done_d,
+                                      E, (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step,
+                                      traj ? (int64_t)act_block : 0);
+            for (int t = 0; e == hipSuccess && !g->day_kernel && t < p.T; ++t) {
+                float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
+                e = launch_policy(policy->d_img, policy->image, obs0 + (size_t)t * (size_t)obs_step,
+                                  noise ? noise + (size_t)t * act_block : nullptr, a_d + (traj ? (size_t)t * act_block : 0),
+                                  policy->d_env_actions, E, cs);
+                if (e == hipSuccess)
+                    e = launch_step(pd, ds, ipd, env->host_tab, policy->d_env_actions, obs_t,
+                                    reward_d + (size_t)t * (size_t)out_step, done_d + (size_t)t * (size_t)out_step, E, t,
+                                    (vec && aligned16(obs_t)) ? 1 : 0, cs);
+            }
+        } else if (g->day_kernel) {
             if (e == hipSuccess)
                 e = launch_day(pd, ds, ipd, actions, obs_d, reward_d, done_d, E, 0, p.T,
                                (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step);
@@ -152,6 +179,21 @@ int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *rewa
     return SNG_OK;
 }
 
+extern "C" {
+
+int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
+                     const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out) {
+    return capture_days(env, nullptr, actions, nullptr, nullptr, obs, reward, done, info, flags, days, day_returns, out);
+}
+
+int sng_graph_create_policy(SngEnv *env, SngPolicy *policy, const float *noise, float *obs, float *actions_out,
+                            double *reward, uint8_t *done, const SngInfo *info, int flags, int32_t days,
+                            double *day_returns, SngGraph **out) {
+    if (!env || !policy || !actions_out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
+    if (policy->env != env) return fail(env, SNG_ERR_INVALID_ARGUMENT, "the policy was created for another env");
+    return capture_days(env, policy, nullptr, noise, actions_out, obs, reward, done, info, flags, days, day_returns, out);
+}
+
 int sng_graph_launch(SngGraph *g, void *stream) {
     if (!g) return SNG_ERR_INVALID_ARGUMENT;
     SngEnv *env = g->env;
@@ -181,7 +223,7 @@ int sng_graph_launch(SngGraph *g, void *stream) {
 
 int sng_graph_step_nodes(const SngGraph *g) {
     if (!g) return -1;
-    return g->day_kernel ? 1 : g->env->p.T;
+    return g->day_kernel ? 1 : g->policy ? 2 * g->env->p.T : g->env->p.T;
 }
 
 int sng_graph_reset_overlapped(const SngGraph *g) {

@@ -37,6 +37,7 @@
 #include "sng_step_day.h"       // day_wide_kernel, day_lean_kernel
 #include "sng_step_general.h"   // step_kernel
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
+#include "sng_policy.h"         // mlp_actor_tile, policy_kernel
 
 namespace sng {
 
@@ -399,6 +400,89 @@ __global__ void bump_day_kernel(DeviceState s, uint64_t amount) {
 hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t amount) {
     hipLaunchKernelGGL(bump_day_kernel, dim3(1), dim3(1), 0, stream, s, amount);
     return hipGetLastError();
+}
+
+int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force) {
+    return policy_day_form(step_plan(p, info_diag(info)), trajectory, step_nodes, force) == POLICY_FUSED ? 1 : 0;
+}
+
+typedef void (*PolicyDayKernel)(const float *, PolicyImage, const float *, int64_t, int, const float *, float *, float *,
+                                double *, uint8_t *, int64_t, int, int, int, int, int64_t, int64_t, int64_t, Params,
+                                DeviceState, InfoPtrs);
+// an instantiation policy_day_compiled (sng_step_plan.h) leaves out is not instantiated
+template <int NC, bool PK, bool REQ>
+static PolicyDayKernel policy_day_entry() {
+    if constexpr (policy_day_compiled(NC, PK, REQ)) return day_lean_policy_kernel<NC, PK, REQ>;
+    else return nullptr;
+}
+template <int NC>
+static StepLaunch policy_day_launch(const StepPlan &pl, int64_t E, PolicyDayKernel &kern) {
+    kern = policy_day_entry<NC, false, false>();
+    if (pl.pk && pl.req) kern = policy_day_entry<NC, true, true>();
+    else if (pl.pk) kern = policy_day_entry<NC, true, false>();
+    else if (pl.req) kern = policy_day_entry<NC, false, true>();
+    return {nullptr, nullptr, blocks_for(E, kLeanBlock), dim3(kLeanBlock), PolicyDayLds<NC>::BYTES};
+}
+
+hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *img,
+                             const PolicyImage &m, const float *noise, const float *obs0, float *obs,
+                             float *actions_out, double *reward, uint8_t *done, int64_t E, int vec_io,
+                             hipStream_t stream, int64_t obs_step, int64_t out_step, int64_t act_step) {
+    const StepPlan pl = step_plan(p, info_diag(info));
+    if (policy_day_form(pl, obs_step != 0 || out_step != 0, false, true) != POLICY_FUSED) return hipErrorNotSupported;
+    if (m.O != p.obs_dim || m.A != p.act_dim) return hipErrorInvalidValue;
+    PolicyDayKernel kern = nullptr;
+    StepLaunch l;
+    switch (pl.nc) {   // the lean sizes of kStationSizes
+        case 1: l = policy_day_launch<1>(pl, E, kern); break;
+        case 2: l = policy_day_launch<2>(pl, E, kern); break;
+        case 4: l = policy_day_launch<4>(pl, E, kern); break;
+        case 8: l = policy_day_launch<8>(pl, E, kern); break;
+        case 10: l = policy_day_launch<10>(pl, E, kern); break;
+        case 16: l = policy_day_launch<16>(pl, E, kern); break;
+    }
+    if (!kern) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
+    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
+    // every step's block 16 B aligned, or none is promised to be
+    const int64_t noise_step = noise ? E * (int64_t)p.act_dim : 0;
+    if (obs_step % 4 != 0 || !a16(obs0) || !a16(noise) || noise_step % 4 != 0) vec_io = 0;
+    const int vec_act = (a16(actions_out) && act_step % 4 == 0) ? 1 : 0;
+    // without noise the prefetch reads step 0's block of a, which is never used
+    return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, img, m, noise ? noise : actions_out,
+                         noise_step, noise ? 1 : 0, obs0, obs, actions_out, reward, done, E, 0, p.T, vec_io, vec_act,
+                         obs_step, out_step, act_step, p, s, info);
+}
+
+// One workgroup's tiles are more than 64 KB of dynamic LDS from 46 chargers on (150,528 B at 128): allowed once
+// per kernel, up to the CU's 160 KB, and asked for when the first policy is created -- outside any stream capture.
+constexpr int kPolicyMaxLds = 160 * 1024;
+hipError_t policy_kernels_init() {
+    static const hipError_t set = [] {
+        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_kernel<false>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
+        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
+        return a != hipSuccess ? a : b;
+    }();
+    return set;
+}
+
+template <bool TANH>
+static hipError_t launch_policy_kernel(const float *img, const PolicyImage &m, const float *obs, const float *noise,
+                                       float *actions, float *env_actions, int64_t E, hipStream_t stream) {
+    const size_t lds = policy_lds_bytes(m.O, m.A);
+    if (lds > (size_t)kPolicyMaxLds) return hipErrorInvalidValue;
+    if (lds > 64u * 1024u && policy_kernels_init() != hipSuccess) return policy_kernels_init();
+    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
+    const int vec = (a16(obs) && a16(noise) && a16(actions) && a16(env_actions)) ? 1 : 0;
+    return launch_kernel(policy_kernel<TANH>, blocks_for(E, kWave), dim3(kPolicyBlock), lds, stream, nullptr, nullptr, img, m,
+                         obs, noise, actions, env_actions, E, vec);
+}
+
+hipError_t launch_policy(const float *img, const PolicyImage &m, const float *obs, const float *noise, float *actions,
+                         float *env_actions, int64_t E, hipStream_t stream) {
+    return m.activation == POLICY_RELU ? launch_policy_kernel<false>(img, m, obs, noise, actions, env_actions, E, stream)
+                                       : launch_policy_kernel<true>(img, m, obs, noise, actions, env_actions, E, stream);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sng_layout.h"
+#include "sng_policy_host.h"
 
 namespace sng {
 
@@ -41,6 +42,23 @@ hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipS
 hipError_t launch_mt_prepare(const RefStreams &rs, int64_t E, hipStream_t stream);
 hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStreams &rs, int64_t E, int i4, int i10,
                           int i1, bool prepare, hipStream_t stream);
+// The MLP actor over E rows (sng_policy.h, policy_kernel): img is the device image `m` describes; noise and
+// env_actions may be null.
+hipError_t launch_policy(const float *img, const PolicyImage &m, const float *obs, const float *noise, float *actions,
+                         float *env_actions, int64_t E, hipStream_t stream);
+// The policy kernels' dynamic-LDS limit, raised once (stations above 45 chargers need more than 64 KB); called by
+// sng_policy_create so that no capture is the first to ask.
+hipError_t policy_kernels_init();
+// 1: a captured policy day of this plan is one fused node (sng_step_plan.h policy_day_form), 0: T x (policy, step)
+int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force);
+// A whole day with the actor between the steps in one launch (sng_policy.h, day_lean_policy_kernel), for a plan
+// with the fused form (hipErrorNotSupported otherwise).  noise: T blocks or null; obs0: the day's t = 0 observation
+// block; obs, reward, done: step 0's blocks, obs_step / out_step as launch_day's; actions_out: step 0's block of a,
+// act_step floats to the next step's (0: one block).
+hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *img,
+                             const PolicyImage &m, const float *noise, const float *obs0, float *obs,
+                             float *actions_out, double *reward, uint8_t *done, int64_t E, int vec_io,
+                             hipStream_t stream, int64_t obs_step, int64_t out_step, int64_t act_step);
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

@@ -103,6 +103,23 @@ inline DayFamily day_kernel_of(const StepPlan &pl, bool trajectory) {
     if (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10 && !trajectory) return DAY_WIDE;
     return DAY_NONE;
 }
+// The form of a captured day with the MLP actor in the loop (sng_graph_create_policy).  Decided here and nowhere
+// else.  POLICY_NODES: T x (policy_kernel node, step node), the step nodes being the plan's own step kernel.
+// POLICY_FUSED: day_lean_policy_kernel<NC, PK, REQ> (sng_policy.h), the actor between the steps of the plan's lean day
+// kernel, one node a day.  It exists where day_lean_kernel does and policy_day_compiled says so (zero scratch, zero
+// VGPR spills: tests/test_policy_kernel_resources.py); the wide N = 10 and N = 50 plans, the general kernel's
+// stations, any diagnostics and SNG_GRAPH_STEP_NODES (`step_nodes`) take nodes.  Where it exists it is the default
+// only where its day measured shorter than the node form's by more than the node form's own spread
+// (policy_day_faster; profiles/policy_day_ab.txt); SNG_GRAPH_POLICY_FUSED (`force`: A/B runs
+// and tests) takes it wherever it is compiled.
+enum PolicyDayForm : int { POLICY_NODES, POLICY_FUSED };
+constexpr bool policy_day_compiled(int nc, bool pk, bool req) { return day_lean_compiled(nc, pk, req); }
+constexpr bool policy_day_faster(int /*nc*/) { return false; }
+inline PolicyDayForm policy_day_form(const StepPlan &pl, bool trajectory, bool step_nodes, bool force = false) {
+    if (step_nodes || day_kernel_of(pl, trajectory) != DAY_LEAN || !policy_day_compiled(pl.nc, pl.pk, pl.req))
+        return POLICY_NODES;
+    return (policy_day_faster(pl.nc) || force) ? POLICY_FUSED : POLICY_NODES;
+}
 // A device-RNG reset is one launch -- the t = 0 observation as extra blocks of the generator's grid -- while the
 // observation blocks' [kGenObsEnvs][obs_dim] LDS tile stays small next to the vehicle lists (32 KB: up to 60
 // chargers); wider stations run profile_kernel and observe0_kernel behind the generator (launch_generate).

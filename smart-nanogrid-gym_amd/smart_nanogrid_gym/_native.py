@@ -27,6 +27,7 @@ GRAPH_STEP_NODES = 2   # sng.h SNG_GRAPH_STEP_NODES
 GRAPH_TRAJECTORY = 4   # sng.h SNG_GRAPH_TRAJECTORY
 GRAPH_SERIAL_RESET = 8   # sng.h SNG_GRAPH_SERIAL_RESET
 GRAPH_OVERLAPPED_RESET = 16   # sng.h SNG_GRAPH_OVERLAPPED_RESET
+GRAPH_POLICY_FUSED = 32   # sng.h SNG_GRAPH_POLICY_FUSED
 FLAG_NEGATIVE_DEMAND = 0x1
 FLAG_CHARGING_MODE = 0x2
 FLAG_BESS_SOC_ABOVE_1 = 0x4
@@ -103,6 +104,15 @@ class SngScenario(ctypes.Structure):
                 ("pv_ratio", c_double_p)]
 
 
+class SngMlpSpec(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("activation", ctypes.c_int32), ("clip_low", c_float_p), ("clip_high", c_float_p)]
+
+
+class SngMlpWeights(ctypes.Structure):
+    _fields_ = [(f, c_float_p) for f in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -147,6 +157,16 @@ EXPORTS = {
     "sng_time_step_kernels": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int32, c_float_p,
                                              c_float_p, _S]),
+    "sng_policy_create": (ctypes.c_int, [_H, ctypes.POINTER(SngMlpSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_policy_set_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngMlpWeights), _S]),
+    "sng_policy_actions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, _S]),
+    "sng_policy_destroy": (None, [ctypes.c_void_p]),
+    "sng_graph_create_policy": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_policy_host_actions": (ctypes.c_int, [ctypes.POINTER(SngMlpSpec), ctypes.POINTER(SngMlpWeights),
+                                               ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_float_p]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

@@ -239,6 +239,7 @@ class SmartNanogridVecEnv(_VecEnvBase):
         self.info_d = {}
         self.charger_power_d = self.vehicle_soc_d = None
         self._recorders = []
+        self._actors = []   # weak references to the MlpActors made for this batch (policy.py): closed before it
         self._info = _native.SngInfo()
         # errors are watched through the summary word (touched only when an env raises a flag), so the
         # step stores no per-env flags; info=True adds the per-step per-env flags to the diagnostics
@@ -271,6 +272,10 @@ class SmartNanogridVecEnv(_VecEnvBase):
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if not self.closed and getattr(self, "_h", None):
+            for ref in getattr(self, "_actors", ()):
+                actor = ref()
+                if actor is not None:
+                    actor.close()
             torch.cuda.synchronize(self.device)
             lib().sng_destroy(self._h)
             self._h = None

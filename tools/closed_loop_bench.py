@@ -34,6 +34,21 @@ import torch  # noqa: E402
 from smart_nanogrid_gym import RuleBasedController, SmartNanogridVecEnv  # noqa: E402
 
 
+def mlp_policy(venv, seed):
+    """The --policy mlp actor: SB3's MlpPolicy-shaped network (64-64 tanh, fp32, random init from `seed`) on the env's
+    device and the policy callable obs -> the action mean clipped to the Box.  tools/policy_day_ab.py times the same."""
+    torch.manual_seed(seed)
+    net = torch.nn.Sequential(torch.nn.Linear(venv.obs_dim, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64),
+                              torch.nn.Tanh(), torch.nn.Linear(64, venv.act_dim)).to(venv.device)
+    low = torch.tensor(venv.action_space.low, device=venv.device)
+    high = torch.tensor(venv.action_space.high, device=venv.device)
+
+    @torch.no_grad()
+    def ctl(obs):
+        return torch.maximum(torch.minimum(net(obs), high), low)
+    return net, ctl
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -53,15 +68,7 @@ def main():
         ctl = RuleBasedController(N)
         policy_desc = "RuleBasedController (solvers/RBC/rbc.py) on device obs"
     else:
-        torch.manual_seed(args.seed)
-        net = torch.nn.Sequential(torch.nn.Linear(venv.obs_dim, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64),
-                                  torch.nn.Tanh(), torch.nn.Linear(64, venv.act_dim)).to(venv.device)
-        low = torch.tensor(venv.action_space.low, device=venv.device)
-        high = torch.tensor(venv.action_space.high, device=venv.device)
-
-        @torch.no_grad()
-        def ctl(obs):
-            return torch.maximum(torch.minimum(net(obs), high), low)
+        _, ctl = mlp_policy(venv, args.seed)
         policy_desc = "SB3 MlpPolicy-shaped actor (64-64 tanh, fp32, random init), action mean clipped to the Box"
     T = venv.timesteps
     total = torch.zeros(E, dtype=torch.float64, device=venv.device)

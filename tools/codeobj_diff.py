@@ -4,8 +4,9 @@
   tools/codeobj_diff.py <parent libsng.so> <this libsng.so>
 
 A byte-identical code object is reported as such.  Otherwise, per kernel symbol: the disassembly with its
-addresses and encodings stripped, and the kernel's entry in the AMDHSA metadata note; the two symbol sets must be
-equal.  Prints "N kernels, D differ" and exits 1 when D > 0 or the sets differ."""
+addresses and encodings stripped, and the kernel's entry in the AMDHSA metadata note.  Symbols that only one build
+has are listed (a feature adds kernels; a removed one fails), and the symbols both have are compared all the same.
+Prints "N kernels, D differ" and exits 1 when D > 0 or the parent has a symbol this build lacks."""
 import os
 import re
 import shutil
@@ -36,7 +37,7 @@ def functions(co):
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":   # "...": the padding up to the next symbol
             ins = line.split("//")[0].strip()
             if cur and cur[-1].startswith("s_getpc_b64"):
                 ins = re.sub(r"0x[0-9a-f]+$", "<rel>", ins)
@@ -67,15 +68,18 @@ def main(a, b):
         with open(ca, "rb") as fa, open(cb, "rb") as fb:
             same = fa.read() == fb.read()
         fa, fb, ma, mb = functions(ca), functions(cb), metadata(ca), metadata(cb)
-    if set(fa) != set(fb) or set(ma) != set(mb):
-        print("symbol sets differ:", sorted(set(fa) ^ set(fb) | set(ma) ^ set(mb)))
-        return 1
-    differ = sorted(k for k in fa if fa[k] != fb[k] or ma.get(k) != mb.get(k))
-    print(f"{len(ma)} kernels ({len(fa)} symbols), {len(differ)} differ in disassembly or AMDHSA metadata"
-          + ("; code objects byte-identical" if same else ""))
+    removed, added = sorted((set(fa) | set(ma)) - (set(fb) | set(mb))), sorted((set(fb) | set(mb)) - (set(fa) | set(ma)))
+    for k in removed:
+        print("  only in the parent:", k)
+    for k in added:
+        print("  only in this build:", k)
+    shared = sorted(set(fa) & set(fb))
+    differ = [k for k in shared if fa[k] != fb[k] or ma.get(k) != mb.get(k)]
+    print(f"{len(set(ma) & set(mb))} kernels ({len(shared)} symbols) in both, {len(differ)} differ in disassembly or "
+          f"AMDHSA metadata; {len(added)} added, {len(removed)} removed" + ("; code objects byte-identical" if same else ""))
     for k in differ:
         print("  differs:", k)
-    return 1 if differ else 0
+    return 1 if differ or removed else 0
 
 
 if __name__ == "__main__":
