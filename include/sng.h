@@ -423,6 +423,57 @@ int sng_graph_create_policy(SngEnv *env, SngPolicy *policy, const float *noise, 
 int sng_policy_host_actions(const SngMlpSpec *spec, const SngMlpWeights *w, int64_t rows, const float *obs,
                             const float *noise, float *actions, float *env_actions);
 
+/* ---------------------------------------------------------------------------------------------
+ * Actors of any width, and the squashed output: SB3's DDPG / TD3 actor (solvers/RL/ddpg_train.py;
+ * Linear(O, 400) - ReLU - Linear(400, 300) - ReLU - Linear(300, A) - Tanh, rescaled into the action Box), SAC's
+ * 256-256 and a PPO actor with its own net_arch.
+ *
+ * The contract is SngMlpSpec's, with two hidden widths of their own: every layer's output j is the k-ordered float32
+ * fmaf chain started from the bias, over the layer's real K inputs.  The device (policy_net_kernel, on the f32-input
+ * MFMA, whose result is that chain) may append zero-input, zero-weight terms after a chain's last real term, and a
+ * chain with such terms gives +0 where the chain without them gives -0: that sign of a zero is the only bit the
+ * padding can change, so device and host are compared by value (==), and with relu hidden layers they are equal
+ * that way; with tanh they are equal up to the device's tanhf.
+ *
+ * output = SNG_MLP_OUT_MEAN: as SngMlpSpec -- a = mean (+ noise), and the env is stepped with min(max(a, low), high)
+ * where bounds are given, else with a.
+ * output = SNG_MLP_OUT_SQUASH: s = tanh(mean); with noise s = min(max(s + noise, -1), 1) (SB3's _sample_action: the
+ * noise is added and clipped in the [-1, 1] domain); a = s is what is stored; and the env is stepped with SB3's
+ * unscale_action as numpy evaluates it in float32,
+ *     env = low[j] + ((0.5f * (s + 1.0f)) * d[j]),   d[j] = high[j] - low[j] (float32, computed once per policy),
+ * the product and the sum each rounded on their own (no fused multiply-add).  low / high are the action Box and
+ * must be finite.
+ *
+ * Refusals: a hidden width outside 8 .. 512, an act_dim above 64 (the kernel keeps two output tiles of 32: stations
+ * of up to 63 chargers with a battery, 64 without; the message names act_dim), or a combination of widths and obs_dim
+ * whose LDS tiles do not fit a compute unit's 160 KB (the message names the sizes), is SNG_ERR_UNSUPPORTED -- every
+ * pair of widths up to 512 fits at stations of up to 50 chargers (obs_dim 109).  sng_policy_net_host_actions refuses
+ * the same specs, although the host model itself has no such limits.  Dims that are not the env's, a bad activation or output,
+ * bounds that are unordered, half given or (SQUASH) missing or not finite, and non-finite weights are
+ * SNG_ERR_INVALID_ARGUMENT. */
+#define SNG_MLP_OUT_MEAN   0   /* as SngMlpSpec: a = mean (+ noise); env action = clip(a) where bounds are given */
+#define SNG_MLP_OUT_SQUASH 1   /* s = tanh(mean); with noise s = min(max(s + noise, -1), 1); a = s is stored;
+                                  env action = low + (0.5f * (s + 1.0f)) * (high - low)                          */
+typedef struct SngMlpNetSpec {
+    int32_t obs_dim, act_dim;
+    int32_t hidden1, hidden2;      /* each 8 .. 512, any integer */
+    int32_t activation;            /* hidden layers: 0 tanh, 1 relu */
+    int32_t output;                /* SNG_MLP_OUT_* */
+    const float *low, *high;       /* host [act_dim]: MEAN: clip bounds or both NULL; SQUASH: the Box, required */
+} SngMlpNetSpec;
+/* An actor of that net for `env`.  SngMlpWeights holds w1 [hidden1][obs_dim], w2 [hidden2][hidden1] and
+ * w3 [act_dim][hidden2] with their biases.  The policy that comes back is sng_policy_create's in every other call:
+ * sng_policy_set_weights, sng_policy_actions (one policy_net_kernel launch; a 64-64 MEAN net runs that kernel too),
+ * sng_graph_create_policy and sng_policy_destroy.  Its captured days are always in node form, T x
+ * (policy_net_kernel node, step node): SNG_GRAPH_POLICY_FUSED is accepted and gives nodes
+ * (csrc/sng_step_plan.h, policy_net_day_form). */
+int sng_policy_create_net(SngEnv *env, const SngMlpNetSpec *spec, SngPolicy **out);
+/* Host only: that contract on the CPU (csrc/sng_policy_net_host.h, mlp_net_host), over the chains' real terms.
+ * For a 64-64 MEAN spec it gives what sng_policy_host_actions gives.  Validates as sng_policy_create_net and
+ * sng_policy_set_weights do. */
+int sng_policy_net_host_actions(const SngMlpNetSpec *spec, const SngMlpWeights *w, int64_t rows, const float *obs,
+                                const float *noise, float *actions, float *env_actions);
+
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for
  * `num_envs` envs seeded seed+i; `episode` = number of days already drawn. */

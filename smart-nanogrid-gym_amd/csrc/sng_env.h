@@ -84,6 +84,11 @@ struct SngPolicy {
     SngMlpSpec spec{};
     std::vector<float> clip_low, clip_high;   // owned copies behind spec.clip_low / clip_high
     sng::PolicyImage image{};
+    // sng_policy_create_net: the net's spec and image (sng_policy_net_host.h) in the place of spec and image; its
+    // bounds are kept in clip_low / clip_high too
+    bool net = false;
+    SngMlpNetSpec net_spec{};
+    sng::NetImage net_image{};
     float *d_img = nullptr, *h_img = nullptr;
     float *d_env_actions = nullptr;           // [E][act_dim]
     hipEvent_t uploaded = nullptr;            // the last upload has read h_img

@@ -6,6 +6,20 @@
 
 using namespace sng;
 
+// The form of a policy's captured day: sng_step_plan.h decides it, per kind of policy (sng_policy_create's 64-64
+// actor, sng_policy_create_net's actor of any width).
+static bool policy_graph_fused(const SngPolicy *policy, const Params &p, const InfoPtrs &ip, bool traj, bool step_nodes,
+                               bool force) {
+    if (policy->net) return policy_net_day_fused(p, ip, traj, step_nodes, force) != 0;
+    return policy_day_fused(p, ip, traj, step_nodes, force) != 0;
+}
+// One actor launch over the env's rows, by the policy's own kernel.
+static hipError_t launch_actor(const SngPolicy *policy, const float *obs, const float *noise, float *actions,
+                               float *env_actions, int64_t E, hipStream_t stream) {
+    if (policy->net) return launch_policy_net(policy->d_img, policy->net_image, obs, noise, actions, env_actions, E, stream);
+    return launch_policy(policy->d_img, policy->image, obs, noise, actions, env_actions, E, stream);
+}
+
 // sng_graph_create and sng_graph_create_policy.  Without a policy, `actions` holds the day's T action blocks.  With
 // one (sng_policy.cpp), every step's actions are the actor's answer to the observation before it: `noise` (T
 // blocks, may be null) takes the place of the actions stream, `actions_out` receives a, and the step nodes read the
@@ -47,8 +61,9 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
     // with SNG_GRAPH_STEP_NODES -- as T dependent step nodes
     // with a policy: one fused node where the plan has that form (sng_step_plan.h policy_day_form), else T x (policy
     // node, step node)
-    g->day_kernel = policy ? policy_day_fused(p, ip, traj, (flags & SNG_GRAPH_STEP_NODES) != 0,
-                                              (flags & SNG_GRAPH_POLICY_FUSED) != 0) != 0
+    // (a net policy's days are always nodes: policy_net_day_form)
+    g->day_kernel = policy ? policy_graph_fused(policy, p, ip, traj, (flags & SNG_GRAPH_STEP_NODES) != 0,
+                                                (flags & SNG_GRAPH_POLICY_FUSED) != 0)
                            : !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
     // Overlapped (sng_step_plan.h reset_overlapped, day_shape): the generators are captured on a second stream, day
     // d + 1's into the day slot that day d does not use, so it runs beside day d's steps.  The edges are gen(d) ->
@@ -128,9 +143,9 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
                                       traj ? (int64_t)act_block : 0);
             for (int t = 0; e == hipSuccess && !g->day_kernel && t < p.T; ++t) {
                 float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
-                e = launch_policy(policy->d_img, policy->image, obs0 + (size_t)t * (size_t)obs_step,
-                                  noise ? noise + (size_t)t * act_block : nullptr, a_d + (traj ? (size_t)t * act_block : 0),
-                                  policy->d_env_actions, E, cs);
+                e = launch_actor(policy, obs0 + (size_t)t * (size_t)obs_step,
+                                 noise ? noise + (size_t)t * act_block : nullptr, a_d + (traj ? (size_t)t * act_block : 0),
+                                 policy->d_env_actions, E, cs);
                 if (e == hipSuccess)
                     e = launch_step(pd, ds, ipd, env->host_tab, policy->d_env_actions, obs_t,
                                     reward_d + (size_t)t * (size_t)out_step, done_d + (size_t)t * (size_t)out_step, E, t,

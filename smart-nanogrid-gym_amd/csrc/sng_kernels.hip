@@ -38,6 +38,7 @@
 #include "sng_step_general.h"   // step_kernel
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
 #include "sng_policy.h"         // mlp_actor_tile, policy_kernel
+#include "sng_policy_net.h"     // policy_net_kernel
 
 namespace sng {
 
@@ -406,6 +407,10 @@ int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, boo
     return policy_day_form(step_plan(p, info_diag(info)), trajectory, step_nodes, force) == POLICY_FUSED ? 1 : 0;
 }
 
+int policy_net_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force) {
+    return policy_net_day_form(step_plan(p, info_diag(info)), trajectory, step_nodes, force) == POLICY_FUSED ? 1 : 0;
+}
+
 typedef void (*PolicyDayKernel)(const float *, PolicyImage, const float *, int64_t, int, const float *, float *, float *,
                                 double *, uint8_t *, int64_t, int, int, int, int, int64_t, int64_t, int64_t, Params,
                                 DeviceState, InfoPtrs);
@@ -462,7 +467,11 @@ hipError_t policy_kernels_init() {
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
         const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_kernel<true>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
-        return a != hipSuccess ? a : b;
+        const hipError_t c = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_net_kernel<false>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
+        const hipError_t d = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_net_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
+        return a != hipSuccess ? a : b != hipSuccess ? b : c != hipSuccess ? c : d;
     }();
     return set;
 }
@@ -483,6 +492,22 @@ hipError_t launch_policy(const float *img, const PolicyImage &m, const float *ob
                          float *env_actions, int64_t E, hipStream_t stream) {
     return m.activation == POLICY_RELU ? launch_policy_kernel<false>(img, m, obs, noise, actions, env_actions, E, stream)
                                        : launch_policy_kernel<true>(img, m, obs, noise, actions, env_actions, E, stream);
+}
+
+// policy_net_kernel: 64 rows a workgroup; its LDS (hidden1's rows and the shared region) is above 64 KB from a
+// hidden1 of 224 on.
+hipError_t launch_policy_net(const float *img, const NetImage &m, const float *obs, const float *noise, float *actions,
+                             float *env_actions, int64_t E, hipStream_t stream) {
+    static_assert(kNetMaxLds == (size_t)kPolicyMaxLds, "one limit for the policy kernels");
+    const size_t lds = net_lds_bytes(m);
+    if (lds > kNetMaxLds || m.N3 > kNetMaxAct) return hipErrorInvalidValue;   // what net_spec_check refuses
+    if (lds > 64u * 1024u && policy_kernels_init() != hipSuccess) return policy_kernels_init();
+    const dim3 grid = blocks_for(E, kNetRows), block(kNetBlock);
+    return m.activation == POLICY_RELU
+               ? launch_kernel(policy_net_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise,
+                               actions, env_actions, E)
+               : launch_kernel(policy_net_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise,
+                               actions, env_actions, E);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

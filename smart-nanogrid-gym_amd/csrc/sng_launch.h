@@ -6,6 +6,7 @@
 
 #include "sng_layout.h"
 #include "sng_policy_host.h"
+#include "sng_policy_net_host.h"
 
 namespace sng {
 
@@ -46,11 +47,17 @@ hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStream
 // env_actions may be null.
 hipError_t launch_policy(const float *img, const PolicyImage &m, const float *obs, const float *noise, float *actions,
                          float *env_actions, int64_t E, hipStream_t stream);
+// The MLP actor of any width over E rows (sng_policy_net.h, policy_net_kernel): img is the device image `m` describes;
+// noise and env_actions may be null.
+hipError_t launch_policy_net(const float *img, const NetImage &m, const float *obs, const float *noise, float *actions,
+                             float *env_actions, int64_t E, hipStream_t stream);
 // The policy kernels' dynamic-LDS limit, raised once (stations above 45 chargers need more than 64 KB); called by
 // sng_policy_create so that no capture is the first to ask.
 hipError_t policy_kernels_init();
 // 1: a captured policy day of this plan is one fused node (sng_step_plan.h policy_day_form), 0: T x (policy, step)
 int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force);
+// the same for a policy made by sng_policy_create_net (sng_step_plan.h policy_net_day_form: always 0)
+int policy_net_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force);
 // A whole day with the actor between the steps in one launch (sng_policy.h, day_lean_policy_kernel), for a plan
 // with the fused form (hipErrorNotSupported otherwise).  noise: T blocks or null; obs0: the day's t = 0 observation
 // block; obs, reward, done: step 0's blocks, obs_step / out_step as launch_day's; actions_out: step 0's block of a,

@@ -120,6 +120,13 @@ inline PolicyDayForm policy_day_form(const StepPlan &pl, bool trajectory, bool s
         return POLICY_NODES;
     return (policy_day_faster(pl.nc) || force) ? POLICY_FUSED : POLICY_NODES;
 }
+// A policy made by sng_policy_create_net (policy_net_kernel, sng_policy_net.h) has no fused day: its actor is a
+// workgroup of four wavefronts on 64 rows with up to 160 KB of LDS, which no day kernel's wavefront can carry between
+// its steps.  Every plan takes nodes, T x (policy_net_kernel node, step node), whatever is forced.
+inline PolicyDayForm policy_net_day_form(const StepPlan & /*pl*/, bool /*trajectory*/, bool /*step_nodes*/,
+                                         bool /*force*/ = false) {
+    return POLICY_NODES;
+}
 // A device-RNG reset is one launch -- the t = 0 observation as extra blocks of the generator's grid -- while the
 // observation blocks' [kGenObsEnvs][obs_dim] LDS tile stays small next to the vehicle lists (32 KB: up to 60
 // chargers); wider stations run profile_kernel and observe0_kernel behind the generator (launch_generate).

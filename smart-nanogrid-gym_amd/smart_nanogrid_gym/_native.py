@@ -113,6 +113,16 @@ class SngMlpWeights(ctypes.Structure):
     _fields_ = [(f, c_float_p) for f in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
+MLP_OUT_MEAN = 0     # sng.h SNG_MLP_OUT_MEAN
+MLP_OUT_SQUASH = 1   # sng.h SNG_MLP_OUT_SQUASH
+
+
+class SngMlpNetSpec(ctypes.Structure):
+    _fields_ = [("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32),
+                ("hidden2", ctypes.c_int32), ("activation", ctypes.c_int32), ("output", ctypes.c_int32),
+                ("low", c_float_p), ("high", c_float_p)]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -167,6 +177,9 @@ EXPORTS = {
                                                ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "sng_policy_host_actions": (ctypes.c_int, [ctypes.POINTER(SngMlpSpec), ctypes.POINTER(SngMlpWeights),
                                                ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "sng_policy_create_net": (ctypes.c_int, [_H, ctypes.POINTER(SngMlpNetSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_policy_net_host_actions": (ctypes.c_int, [ctypes.POINTER(SngMlpNetSpec), ctypes.POINTER(SngMlpWeights),
+                                                   ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_float_p]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

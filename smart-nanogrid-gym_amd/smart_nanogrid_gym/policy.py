@@ -1,10 +1,13 @@
-"""The policy in the loop: the MLP actor of the reference's own workload, PPO("MlpPolicy", env)
-(solvers/RL/ppo_train.py:92), evaluated by the library between steps.
+"""The policy in the loop: the MLP actors of the reference's own workloads, PPO("MlpPolicy", env)
+(solvers/RL/ppo_train.py:92) and DDPG("MlpPolicy", env) (solvers/RL/ddpg_train.py), evaluated by the library between
+steps.
 
-`MlpActor` is the 64-64 tanh (or relu) actor as a device kernel (include/sng.h, sng_policy_create): a callable from
-observations to env actions, and the host model of the same arithmetic.  `ClosedLoopGraph` captures whole days with
-the actor between the steps (sng_graph_create_policy), so a rollout whose every action answers the observation
-before it is one graph launch, with no torch kernel in it.
+`MlpActor` is the actor as a device kernel: by default the 64-64 tanh (or relu) actor of PPO (include/sng.h,
+sng_policy_create); with another `net_arch` or `squash=True` an actor of any two hidden widths up to 512 on the
+f32-input MFMA (sng_policy_create_net), whose squashed output is SB3's DDPG / TD3 / SAC actor: tanh, noise clipped in
+[-1, 1], rescaled into the action Box.  It is a callable from observations to env actions, and the host model of the
+same arithmetic.  `ClosedLoopGraph` captures whole days with the actor between the steps (sng_graph_create_policy),
+so a rollout whose every action answers the observation before it is one graph launch, with no torch kernel in it.
 """
 import ctypes
 import weakref
@@ -26,6 +29,10 @@ ACTIVATIONS = {"tanh": 0, "relu": 1}
 SB3_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
             "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias",
             "action_net.weight", "action_net.bias")
+# stable-baselines3's TD3Policy (DDPG, TD3) state_dict keys of the actor: mu = Linear, ReLU, Linear, ReLU, Linear, Tanh
+SB3_DDPG_KEYS = ("actor.mu.0.weight", "actor.mu.0.bias", "actor.mu.2.weight", "actor.mu.2.bias",
+                 "actor.mu.4.weight", "actor.mu.4.bias")
+DDPG_NET_ARCH = (400, 300)
 
 
 def _as_f32(x):
@@ -34,16 +41,26 @@ def _as_f32(x):
     return np.ascontiguousarray(x, dtype=np.float32)
 
 
-def actor_weights(weights, obs_dim, act_dim):
-    """Six float32 arrays (w1 [64, obs_dim], b1, w2 [64, 64], b2, w3 [act_dim, 64], b3) from six arrays or tensors
-    in that order, or from a dict holding stable-baselines3's actor keys (SB3_KEYS; other entries are ignored)."""
+def _net_arch(net_arch):
+    arch = tuple(int(h) for h in net_arch)
+    if len(arch) != 2:
+        raise ValueError("net_arch must name two hidden widths")
+    return arch
+
+
+def actor_weights(weights, obs_dim, act_dim, net_arch=(HIDDEN, HIDDEN)):
+    """Six float32 arrays (w1 [h1, obs_dim], b1, w2 [h2, h1], b2, w3 [act_dim, h2], b3; net_arch = (h1, h2)) from six
+    arrays or tensors in that order, or from a dict holding stable-baselines3's actor keys: PPO's (SB3_KEYS) or
+    DDPG's / TD3's (SB3_DDPG_KEYS); other entries are ignored."""
+    h1, h2 = _net_arch(net_arch)
     if isinstance(weights, dict):
-        missing = [k for k in SB3_KEYS if k not in weights]
+        keys = SB3_DDPG_KEYS if SB3_DDPG_KEYS[0] in weights else SB3_KEYS
+        missing = [k for k in keys if k not in weights]
         if missing:
             raise KeyError(f"actor weights: missing {missing}")
-        weights = [weights[k] for k in SB3_KEYS]
+        weights = [weights[k] for k in keys]
     arrs = [_as_f32(w) for w in weights]
-    shapes = [(HIDDEN, obs_dim), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,), (act_dim, HIDDEN), (act_dim,)]
+    shapes = [(h1, obs_dim), (h1,), (h2, h1), (h2,), (act_dim, h2), (act_dim,)]
     if len(arrs) != 6 or any(a.shape != s for a, s in zip(arrs, shapes)):
         raise ValueError(f"actor weights must have shapes {shapes}, got {[a.shape for a in arrs]}")
     return arrs
@@ -57,20 +74,38 @@ def _spec(obs_dim, act_dim, activation, low, high, hidden=HIDDEN):
     return spec
 
 
+def _net_spec(obs_dim, act_dim, activation, low, high, net_arch, squash):
+    h1, h2 = net_arch
+    spec = _native.SngMlpNetSpec(obs_dim, act_dim, h1, h2, ACTIVATIONS[activation],
+                                 _native.MLP_OUT_SQUASH if squash else _native.MLP_OUT_MEAN, None, None)
+    if low is not None:
+        spec.low = low.ctypes.data_as(_native.c_float_p)
+        spec.high = high.ctypes.data_as(_native.c_float_p)
+    return spec
+
+
 def _weights_struct(arrs):
     return _native.SngMlpWeights(*[a.ctypes.data_as(_native.c_float_p) for a in arrs])
 
 
-def host_actions(obs, weights, activation="tanh", low=None, high=None, noise=None):
-    """The actor's contract on the CPU (sng_policy_host_actions): (a, env actions) float32 [rows, act_dim] for
-    observation rows [rows, obs_dim].  low / high: the clip bounds, or None for no clip.  Needs no GPU."""
+def host_actions(obs, weights, activation="tanh", low=None, high=None, noise=None, net_arch=(HIDDEN, HIDDEN),
+                 squash=False, net=False):
+    """The actor's contract on the CPU: (a, env actions) float32 [rows, act_dim] for observation rows
+    [rows, obs_dim].  low / high: the clip bounds, or None for no clip; with squash=True the action Box.  The 64-64
+    actor without squash is sng_policy_host_actions; another net_arch, squash=True or net=True (the diagnostic path
+    of MlpActor's `net`) is sng_policy_net_host_actions, which accepts what sng_policy_create_net accepts: at most 64
+    actions.  Needs no GPU."""
     obs = np.ascontiguousarray(obs, dtype=np.float32)
     rows, obs_dim = obs.shape
-    act_dim = np.shape(weights[4] if not isinstance(weights, dict) else weights[SB3_KEYS[4]])[0]
-    arrs = actor_weights(weights, obs_dim, act_dim)
+    arch = _net_arch(net_arch)
+    if isinstance(weights, dict):
+        last = weights[SB3_DDPG_KEYS[4]] if SB3_DDPG_KEYS[0] in weights else weights[SB3_KEYS[4]]
+    else:
+        last = weights[4]
+    act_dim = np.shape(last)[0]
+    arrs = actor_weights(weights, obs_dim, act_dim, arch)
     if low is not None:
         low, high = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float32), (act_dim,))) for x in (low, high))
-    spec = _spec(obs_dim, act_dim, activation, low, high)
     w = _weights_struct(arrs)
     a = np.zeros((rows, act_dim), np.float32)
     env_a = np.zeros((rows, act_dim), np.float32)
@@ -80,38 +115,59 @@ def host_actions(obs, weights, activation="tanh", low=None, high=None, noise=Non
         if nz.shape != a.shape:
             raise ValueError(f"noise must have shape {a.shape}")
     F = _native.c_float_p
-    check(lib().sng_policy_host_actions(ctypes.byref(spec), ctypes.byref(w), rows, obs.ctypes.data_as(F),
-                                        None if nz is None else nz.ctypes.data_as(F), a.ctypes.data_as(F),
-                                        env_a.ctypes.data_as(F)))
+    args = (rows, obs.ctypes.data_as(F), None if nz is None else nz.ctypes.data_as(F), a.ctypes.data_as(F),
+            env_a.ctypes.data_as(F))
+    if net or squash or arch != (HIDDEN, HIDDEN):
+        spec = _net_spec(obs_dim, act_dim, activation, low, high, arch, squash)
+        check(lib().sng_policy_net_host_actions(ctypes.byref(spec), ctypes.byref(w), *args))
+    else:
+        spec = _spec(obs_dim, act_dim, activation, low, high)
+        check(lib().sng_policy_host_actions(ctypes.byref(spec), ctypes.byref(w), *args))
     return a, env_a
 
 
 class MlpActor:
-    """The 64-64 MLP actor of `venv`'s envs on the device.
+    """An MLP actor of `venv`'s envs on the device.
 
-    activation -- "tanh" (SB3's MlpPolicy) or "relu"
+    activation -- of the hidden layers: "tanh" (SB3's MlpPolicy) or "relu"
     clip       -- True: the env is stepped with the action clipped to venv.action_space, as SB3 clips a Box
-                  action before env.step; False: with the action as it is
+                  action before env.step; False: with the action as it is.  Without meaning with squash=True.
+    net_arch   -- the two hidden widths, each 8 .. 512.  (64, 64) without squash is PPO's actor and policy_kernel
+                  (sng_policy_create), at every station; anything else runs policy_net_kernel on the f32-input MFMA
+                  (sng_policy_create_net), which has two output tiles: venv.act_dim <= 64, i.e. stations of up to 63
+                  chargers with a battery and 64 without.  A wider station is refused (NativeError, libsng error -2).
+    squash     -- True: SB3's DDPG / TD3 / SAC output: a = tanh(mean), with noise clipped to [-1, 1] after the add,
+                  and the env is stepped with a rescaled from [-1, 1] into venv.action_space (unscale_action).
+    net        -- True: the 64-64 actor without squash through policy_net_kernel too.  A diagnostic path: the same
+                  results, for cross-checking the two kernels, and measured slower than the default (20.2 against
+                  17.3 us a launch at 65,536 envs x 8 chargers, profiles/policy_net_ab.txt)
 
-    `actor(obs)` maps a device tensor [rows <= num_envs, obs_dim] to the env actions [rows, act_dim] (one
-    policy_kernel launch on torch's current stream), so the actor is a policy for evaluate_models and
-    tools/closed_loop_bench.py like any torch callable.  `actions(obs, noise)` returns (a, env actions) for the whole
-    batch.  The weights are zero until load()."""
+    `actor(obs)` maps a device tensor [rows <= num_envs, obs_dim] to the env actions [rows, act_dim] (one kernel
+    launch on torch's current stream), so the actor is a policy for evaluate_models and tools/closed_loop_bench.py
+    like any torch callable.  `actions(obs, noise)` returns (a, env actions) for the whole batch.  The weights are
+    zero until load()."""
 
-    def __init__(self, venv, activation="tanh", clip=True):
+    def __init__(self, venv, activation="tanh", clip=True, net_arch=(HIDDEN, HIDDEN), squash=False, net=False):
         if activation not in ACTIVATIONS:
             raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
         self.venv = venv
         self.activation = activation
+        self.net_arch = _net_arch(net_arch)
+        self.squash = bool(squash)
+        self.net = bool(net) or self.squash or self.net_arch != (HIDDEN, HIDDEN)
         self.obs_dim, self.act_dim = venv.obs_dim, venv.act_dim
         self.low = self.high = None
-        if clip:
+        if clip or self.squash:
             self.low = np.ascontiguousarray(venv.action_space.low, dtype=np.float32).reshape(self.act_dim)
             self.high = np.ascontiguousarray(venv.action_space.high, dtype=np.float32).reshape(self.act_dim)
         self.weights = None
-        spec = _spec(self.obs_dim, self.act_dim, activation, self.low, self.high)
         h = ctypes.c_void_p()
-        check(lib().sng_policy_create(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
+        if self.net:
+            spec = _net_spec(self.obs_dim, self.act_dim, activation, self.low, self.high, self.net_arch, self.squash)
+            check(lib().sng_policy_create_net(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
+        else:
+            spec = _spec(self.obs_dim, self.act_dim, activation, self.low, self.high)
+            check(lib().sng_policy_create(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
         self._p = h
         venv._actors.append(weakref.ref(self))   # the env batch closes its actors before itself
         E = venv.num_envs
@@ -119,10 +175,15 @@ class MlpActor:
         self.env_actions_d = torch.zeros((E, self.act_dim), dtype=torch.float32, device=venv.device)
         self._obs_pad = None
 
+    @classmethod
+    def ddpg(cls, venv):
+        """SB3's DDPG("MlpPolicy", env) actor: 400-300, relu, squashed into venv.action_space."""
+        return cls(venv, activation="relu", net_arch=DDPG_NET_ARCH, squash=True)
+
     def load(self, weights):
         """Upload weights: six arrays or tensors (w1, b1, w2, b2, w3, b3 in torch's [out, in] layout) or a dict with
-        SB3's actor keys.  Graphs captured with this actor use them from their next launch on."""
-        arrs = actor_weights(weights, self.obs_dim, self.act_dim)
+        SB3's actor keys (PPO's or DDPG's).  Graphs captured with this actor use them from their next launch on."""
+        arrs = actor_weights(weights, self.obs_dim, self.act_dim, self.net_arch)
         w = _weights_struct(arrs)
         with torch.cuda.device(self.venv.device):
             check(lib().sng_policy_set_weights(self._p, ctypes.byref(w), _stream_handle(self.venv.device)),
@@ -168,7 +229,8 @@ class MlpActor:
         if self.weights is None:
             raise RuntimeError("load() the actor's weights first")
         return host_actions(_as_f32(obs), self.weights, self.activation, self.low, self.high,
-                            None if noise is None else _as_f32(noise))
+                            None if noise is None else _as_f32(noise), net_arch=self.net_arch, squash=self.squash,
+                            net=self.net)
 
     def close(self):
         """Frees the actor's device image and buffers.  Closing the env batch closes its actors first (the library
@@ -189,16 +251,18 @@ class ClosedLoopGraph:
     """Whole days with the actor in the loop, captured once as a hipGraph and replayed: ([device-RNG reset] + T x
     (actor, step)) x days (include/sng.h, sng_graph_create_policy).
 
-    noise      -- optional device tensor [T, E, act_dim] added to the actor's mean, reused every day
+    noise      -- optional device tensor [T, E, act_dim] added to the actor's mean (to tanh(mean) for a squashed
+                  actor: DDPG's action noise, e.g. a precomputed Ornstein-Uhlenbeck path), reused every day
     trajectory -- True: keeps every step: obs_traj [days, T + 1, E, obs_dim], action_traj [days, T, E, act_dim] (a,
-                  before the clip), reward_traj and done_traj [days, T, E]; obs_traj[d, t] is the observation
-                  action_traj[d, t] answered.  False: venv.obs_d / reward_d / done_d and `actions` [E, act_dim] hold
-                  the last step's values.
+                  before the clip or the rescale), reward_traj and done_traj [days, T, E]; obs_traj[d, t] is the
+                  observation action_traj[d, t] answered.  False: venv.obs_d / reward_d / done_d and `actions`
+                  [E, act_dim] hold the last step's values.
     with_reset, days, day_returns, step_nodes -- as EpisodeGraph's.  A steps-only graph steps the loaded day from its
                   t = 0 observation in venv.obs_d.
     fused      -- True: one node a day wherever the station has the fused kernel (the lean stations; sng.h
                   SNG_GRAPH_POLICY_FUSED), also where the node form measured no slower and is the default (the same
-                  results; for A/B and tests).  step_nodes wins over it.
+                  results; for A/B and tests).  step_nodes wins over it.  An actor on policy_net_kernel (another
+                  net_arch, squash) has no fused day: its graphs are nodes whatever is asked.
     New weights loaded into the actor take effect at the next launch, without a recapture."""
 
     def __init__(self, venv, actor, noise=None, days=1, with_reset=True, trajectory=False, day_returns=None,
