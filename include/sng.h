@@ -474,6 +474,69 @@ int sng_policy_create_net(SngEnv *env, const SngMlpNetSpec *spec, SngPolicy **ou
 int sng_policy_net_host_actions(const SngMlpNetSpec *spec, const SngMlpWeights *w, int64_t rows, const float *obs,
                                 const float *noise, float *actions, float *env_actions);
 
+/* ---------------------------------------------------------------------------------------------
+ * The rest of a PPO rollout: critic values, log-probabilities and generalised advantage estimates of the days a
+ * policy graph with SNG_GRAPH_TRAJECTORY left, in one launch.  With them a caller holds everything SB3's RolloutBuffer
+ * holds (observations, actions, rewards, episode starts, values, log-probs, advantages, returns) as device arrays.
+ * The contract is engine-independent, as SngMlpSpec's: one arithmetic, on the host (sng_ppo_host_finish,
+ * csrc/sng_ppo_host.h) and on the device (rollout_gae_kernel, csrc/sng_ppo.h); with relu the device reproduces the host
+ * bit for bit, with tanh the values up to the device's tanhf and the rest exactly, given those values.
+ *
+ * Value net: the second net of SB3's ActorCriticPolicy (mlp_extractor.value_net.{0,2}, value_net), 64-64 with the
+ * actor's activation.  Its arithmetic is SngMlpSpec's with act_dim = 1, no noise and no clip: every output is the
+ * k-ordered float32 fmaf chain started from the bias, and V is the output layer's one chain.  SngMlpWeights holds
+ * w3 [1][64] and b3 [1].
+ *
+ * GAE: numpy's float32 evaluation of RolloutBuffer.compute_returns_and_advantage, per env and per day, walking
+ * t = T-1 .. 0 with gae = 0.0f before t = T-1; every operation is rounded on its own (no fused multiply-add):
+ *     g  = (float)gamma                      gl = (float)((double)gamma * (double)gae_lambda)
+ *     r  = (float)reward[d][t][e]            nn = 1.0f - (float)done[d][t][e]
+ *     delta = ((r + ((g * V[d][t+1][e]) * nn)) - V[d][t][e])
+ *     gae   = delta + ((gl * nn) * gae)
+ *     advantages[d][t][e] = gae              returns[d][t][e] = gae + V[d][t][e]
+ * V[d][T] is the value of obs[d][T] (SB3's last_values, with buffer_size = T).  done is terminal (the env reports no
+ * truncation), so there is no bootstrap through it; days are independent scans, which with the env's own done (1 at
+ * every day's last step) is SB3's one scan over days * T steps.  gamma and gae_lambda must be finite and in [0, 1].
+ *
+ * Log-probability of the sampled action under SB3's DiagGaussianDistribution, from the noise the actor added
+ * (a = mean + noise): inv_std[j] = 1.0f / expf(log_std[j]) is computed once on the host when the weights are uploaded
+ * and stored in the device image next to log_std[j]; per row, in j order, every operation rounded on its own:
+ *     lp = 0.0f;  for j:  z = noise[t][e][j] * inv_std[j]
+ *                         lp = lp + ((((-0.5f * z) * z) - log_std[j]) - 0.91893853f)
+ * noise is sng_graph_create_policy's block [T][num_envs][act_dim], reused every day; logp is [days][T][num_envs] all
+ * the same.  A NULL noise or a NULL logp skips the stage.
+ *
+ * Non-finite value weights and a non-finite log_std are refused at upload, a gamma or gae_lambda outside [0, 1] (or
+ * NaN), days < 1 and a NULL required pointer at the call: SNG_ERR_INVALID_ARGUMENT, the reason in sng_last_error. */
+typedef struct SngPpo SngPpo;
+typedef struct SngPpoRollout {          /* device pointers (host pointers for sng_ppo_host_finish) */
+    int32_t days;
+    double gamma, gae_lambda;
+    const float *obs;                   /* [days][T+1][num_envs][obs_dim] */
+    const double *reward;               /* [days][T][num_envs] */
+    const uint8_t *done;                /* [days][T][num_envs] */
+    const float *noise;                 /* [T][num_envs][act_dim] or NULL */
+    float *values;                      /* [days][T+1][num_envs] */
+    float *advantages, *returns;        /* [days][T][num_envs] */
+    float *logp;                        /* [days][T][num_envs] or NULL */
+} SngPpoRollout;
+/* A head for `env` (its obs_dim, act_dim, T and num_envs); activation: 0 tanh, 1 relu.  The value net's weights and
+ * log_std are zero until sng_ppo_set_weights.  Destroyed before its env, as a policy is. */
+int sng_ppo_create(SngEnv *env, int32_t activation, SngPpo **out);
+/* Upload into the head's device image, asynchronously on `stream`: new weights between two sng_ppo_finish calls
+ * change the next one.  log_std: host [act_dim], or NULL for zeros (SB3's log_std_init). */
+int sng_ppo_set_weights(SngPpo *ppo, const SngMlpWeights *value_net, const float *log_std, void *stream);
+/* One launch (rollout_gae_kernel), asynchronous on `stream`: no synchronisation and no allocation.  Launched after a
+ * day graph on the same stream it finishes that graph's trajectory.  At most 65535 days in one call (more is
+ * SNG_ERR_INVALID_ARGUMENT; the host entry point has no such limit). */
+int sng_ppo_finish(SngPpo *ppo, const SngPpoRollout *rollout, void *stream);
+/* Host only: the same contract on host arrays.  values_given != 0: `values` is read, not computed (obs and value_net
+ * may then be NULL).  Validates as sng_ppo_set_weights and sng_ppo_finish do. */
+int sng_ppo_host_finish(int32_t obs_dim, int32_t act_dim, int32_t activation, int32_t T, int64_t E,
+                        const SngMlpWeights *value_net, const float *log_std, const SngPpoRollout *host_arrays,
+                        int values_given);
+void sng_ppo_destroy(SngPpo *ppo);
+
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for
  * `num_envs` envs seeded seed+i; `episode` = number of days already drawn. */

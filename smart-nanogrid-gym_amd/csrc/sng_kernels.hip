@@ -39,6 +39,7 @@
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
 #include "sng_policy.h"         // mlp_actor_tile, policy_kernel
 #include "sng_policy_net.h"     // policy_net_kernel
+#include "sng_ppo.h"            // rollout_gae_kernel
 
 namespace sng {
 
@@ -508,6 +509,43 @@ hipError_t launch_policy_net(const float *img, const NetImage &m, const float *o
                                actions, env_actions, E)
                : launch_kernel(policy_net_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise,
                                actions, env_actions, E);
+}
+
+// rollout_gae_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises the policy kernels': two observation
+// tiles, the hidden rows and the noise tile are more than 64 KB from 35 chargers on.
+hipError_t ppo_kernels_init() {
+    static const hipError_t set = [] {
+        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_gae_kernel<false>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMaxLds);
+        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_gae_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMaxLds);
+        return a != hipSuccess ? a : b;
+    }();
+    return set;
+}
+
+// Two observation tiles (the step before's is prefetched beside the layers) where they fit a compute unit's LDS with
+// the hidden rows and the noise tile, else one.
+hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoRollout &r, int64_t E, int T,
+                              hipStream_t stream) {
+    const float *noise = r.logp ? r.noise : nullptr;   // no log-probability stage without both
+    const bool two = ppo_lds_bytes(m.v.O, m.A, true, noise != nullptr) <= (size_t)kPpoMaxLds;
+    const size_t lds = ppo_lds_bytes(m.v.O, m.A, two, noise != nullptr);
+    if (lds > (size_t)kPpoMaxLds || T < 1 || E < 1 || r.days < 1 || r.days > kPpoMaxLaunchDays) return hipErrorInvalidValue;
+    if (lds > 64u * 1024u && ppo_kernels_init() != hipSuccess) return ppo_kernels_init();
+    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
+    // every step's block 16 B aligned, or none is promised to be
+    const int vec_obs = (a16(r.obs) && (E * (int64_t)m.v.O) % 4 == 0) ? 1 : 0;
+    const int vec_noise = (a16(noise) && (E * (int64_t)m.A) % 4 == 0) ? 1 : 0;
+    const dim3 grid((unsigned)((E + kWave - 1) / kWave), (unsigned)r.days), block(kPolicyBlock);
+    const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
+    return m.v.activation == POLICY_RELU
+               ? launch_kernel(rollout_gae_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs,
+                               r.reward, r.done, noise, r.values, r.advantages, r.returns, r.logp, E, T, g, gl,
+                               two ? 1 : 0, vec_obs, vec_noise)
+               : launch_kernel(rollout_gae_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs,
+                               r.reward, r.done, noise, r.values, r.advantages, r.returns, r.logp, E, T, g, gl,
+                               two ? 1 : 0, vec_obs, vec_noise);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

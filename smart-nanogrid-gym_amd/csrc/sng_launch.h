@@ -7,6 +7,7 @@
 #include "sng_layout.h"
 #include "sng_policy_host.h"
 #include "sng_policy_net_host.h"
+#include "sng_ppo_host.h"
 
 namespace sng {
 
@@ -66,6 +67,12 @@ hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPt
                              const PolicyImage &m, const float *noise, const float *obs0, float *obs,
                              float *actions_out, double *reward, uint8_t *done, int64_t E, int vec_io,
                              hipStream_t stream, int64_t obs_step, int64_t out_step, int64_t act_step);
+// What finishes a PPO rollout (sng_ppo.h, rollout_gae_kernel): values, advantages, returns and, with noise and logp
+// both given, log-probabilities of `r`'s days of T steps of E envs; img is the device image `m` describes.
+hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoRollout &r, int64_t E, int T,
+                              hipStream_t stream);
+// rollout_gae_kernel's dynamic-LDS limit, raised once; called by sng_ppo_create so that no capture is the first to ask.
+hipError_t ppo_kernels_init();
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

@@ -123,6 +123,13 @@ class SngMlpNetSpec(ctypes.Structure):
                 ("low", c_float_p), ("high", c_float_p)]
 
 
+class SngPpoRollout(ctypes.Structure):
+    _fields_ = [("days", ctypes.c_int32), ("gamma", ctypes.c_double), ("gae_lambda", ctypes.c_double),
+                ("obs", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("noise", ctypes.c_void_p), ("values", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
+                ("returns", ctypes.c_void_p), ("logp", ctypes.c_void_p)]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -180,6 +187,13 @@ EXPORTS = {
     "sng_policy_create_net": (ctypes.c_int, [_H, ctypes.POINTER(SngMlpNetSpec), ctypes.POINTER(ctypes.c_void_p)]),
     "sng_policy_net_host_actions": (ctypes.c_int, [ctypes.POINTER(SngMlpNetSpec), ctypes.POINTER(SngMlpWeights),
                                                    ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "sng_ppo_create": (ctypes.c_int, [_H, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_ppo_set_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngMlpWeights), c_float_p, _S]),
+    "sng_ppo_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngPpoRollout), _S]),
+    "sng_ppo_host_finish": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int64, ctypes.POINTER(SngMlpWeights), c_float_p,
+                                           ctypes.POINTER(SngPpoRollout), ctypes.c_int]),
+    "sng_ppo_destroy": (None, [ctypes.c_void_p]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

@@ -8,6 +8,9 @@ f32-input MFMA (sng_policy_create_net), whose squashed output is SB3's DDPG / TD
 [-1, 1], rescaled into the action Box.  It is a callable from observations to env actions, and the host model of the
 same arithmetic.  `ClosedLoopGraph` captures whole days with the actor between the steps (sng_graph_create_policy),
 so a rollout whose every action answers the observation before it is one graph launch, with no torch kernel in it.
+`PpoHead` is the rest of what a PPO update reads, in one more kernel: the critic's values, the advantages and returns
+and the log-probabilities of such a trajectory (sng_ppo_finish); `PpoRollout` is the graph and that kernel as one
+object that holds what SB3's RolloutBuffer holds.
 """
 import ctypes
 import weakref
@@ -33,6 +36,12 @@ SB3_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bia
 SB3_DDPG_KEYS = ("actor.mu.0.weight", "actor.mu.0.bias", "actor.mu.2.weight", "actor.mu.2.bias",
                  "actor.mu.4.weight", "actor.mu.4.bias")
 DDPG_NET_ARCH = (400, 300)
+# stable-baselines3's ActorCriticPolicy state_dict keys of the critic (value_net's two Linear layers and the value
+# output) and of the Gaussian head's log standard deviations
+SB3_VALUE_KEYS = ("mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
+                  "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias",
+                  "value_net.weight", "value_net.bias")
+SB3_LOG_STD_KEY = "log_std"
 
 
 def _as_f32(x):
@@ -245,6 +254,247 @@ class MlpActor:
             self.close()
         except Exception:
             pass
+
+
+def value_weights(weights, obs_dim):
+    """The value net's six float32 arrays (w1 [64, obs_dim], b1, w2 [64, 64], b2, w3 [1, 64], b3 [1]) from six arrays
+    or tensors in that order, or from a dict holding stable-baselines3's ActorCriticPolicy keys (SB3_VALUE_KEYS);
+    other entries are ignored."""
+    if isinstance(weights, dict):
+        missing = [k for k in SB3_VALUE_KEYS if k not in weights]
+        if missing:
+            raise KeyError(f"value net weights: missing {missing}")
+        weights = [weights[k] for k in SB3_VALUE_KEYS]
+    return actor_weights(weights, obs_dim, 1)
+
+
+def head_weights(weights, obs_dim, act_dim, log_std=None):
+    """(value net arrays, log_std float32 [act_dim]) of a PPO head.  A dict gives log_std under SB3's `log_std` key
+    unless log_std is passed; with six arrays a log_std of None is zeros (SB3's log_std_init)."""
+    if log_std is None:
+        if isinstance(weights, dict):
+            if SB3_LOG_STD_KEY not in weights:
+                raise KeyError(f"ppo head: missing ['{SB3_LOG_STD_KEY}']")
+            log_std = weights[SB3_LOG_STD_KEY]
+        else:
+            log_std = np.zeros(act_dim, np.float32)
+    log_std = _as_f32(log_std).reshape(-1)
+    if log_std.shape != (act_dim,):
+        raise ValueError(f"log_std must have shape {(act_dim,)}, got {log_std.shape}")
+    return value_weights(weights, obs_dim), log_std
+
+
+def _rollout_struct(days, gamma, gae_lambda, ptr, obs, reward, done, noise, values, advantages, returns, logp):
+    p = lambda x: None if x is None else ptr(x)   # noqa: E731
+    return _native.SngPpoRollout(int(days), float(gamma), float(gae_lambda), p(obs), p(reward), p(done), p(noise),
+                                 p(values), p(advantages), p(returns), p(logp))
+
+
+def ppo_host_finish(obs, reward, done, weights=None, log_std=None, noise=None, gamma=0.99, gae_lambda=0.95,
+                    activation="tanh", values=None):
+    """What finishes a PPO rollout, on the CPU (sng_ppo_host_finish): (values [days, T + 1, E], advantages, returns
+    [days, T, E], log_prob [days, T, E] or None without noise) for obs [days, T + 1, E, obs_dim], reward and done
+    [days, T, E] and noise [T, E, act_dim].  weights / log_std: as head_weights takes them.  values: given, they are
+    read instead of computed (obs and weights may then be None).  Needs no GPU."""
+    reward = np.ascontiguousarray(reward, dtype=np.float64)
+    done = np.ascontiguousarray(done, dtype=np.uint8)
+    days, T, E = reward.shape
+    if done.shape != reward.shape:
+        raise ValueError(f"done must have shape {reward.shape}")
+    given = values is not None
+    if obs is not None:
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        if obs.ndim != 4 or obs.shape[:3] != (days, T + 1, E):
+            raise ValueError(f"obs must have shape {(days, T + 1, E, 'obs_dim')}")
+    elif not given:
+        raise ValueError("obs is needed where the values are not given")
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float32)
+        if noise.ndim != 3 or noise.shape[:2] != (T, E):
+            raise ValueError(f"noise must have shape {(T, E, 'act_dim')}")
+        act_dim = noise.shape[2]
+    else:   # no log-probability stage: log_std is not read
+        act_dim, log_std = 1, np.zeros(1, np.float32)
+    if obs is not None:
+        obs_dim = obs.shape[3]
+    elif weights is not None:
+        obs_dim = np.shape(weights[SB3_VALUE_KEYS[0]] if isinstance(weights, dict) else weights[0])[1]
+    else:
+        obs_dim = 1
+    w = None
+    if weights is not None:
+        arrs, log_std = head_weights(weights, obs_dim, act_dim, log_std)
+        w = ctypes.byref(_weights_struct(arrs))
+    else:
+        log_std = np.zeros(act_dim, np.float32) if log_std is None else _as_f32(log_std).reshape(act_dim)
+    if given:
+        vals = np.ascontiguousarray(values, dtype=np.float32).copy()
+        if vals.shape != (days, T + 1, E):
+            raise ValueError(f"values must have shape {(days, T + 1, E)}")
+    else:
+        vals = np.zeros((days, T + 1, E), np.float32)
+    adv, ret = np.zeros((days, T, E), np.float32), np.zeros((days, T, E), np.float32)
+    logp = None if noise is None else np.zeros((days, T, E), np.float32)
+    r = _rollout_struct(days, gamma, gae_lambda, lambda x: x.ctypes.data, obs, reward, done, noise, vals, adv, ret, logp)
+    check(lib().sng_ppo_host_finish(obs_dim, act_dim, ACTIVATIONS[activation], T, E, w,
+                                    None if log_std is None else log_std.ctypes.data_as(_native.c_float_p),
+                                    ctypes.byref(r), 1 if given else 0))
+    return vals, adv, ret, logp
+
+
+class PpoHead:
+    """What a PPO update reads beside the trajectory, on the device (include/sng.h, sng_ppo_create): the 64-64 value
+    net of SB3's MlpPolicy with the actor's activation, the Gaussian head's log_std, and one kernel
+    (rollout_gae_kernel) from a trajectory to critic values, advantages, returns and log-probabilities.  The weights
+    are zero until load()."""
+
+    def __init__(self, venv, activation="tanh"):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
+        self.venv = venv
+        self.activation = activation
+        self.obs_dim, self.act_dim = venv.obs_dim, venv.act_dim
+        self.weights = self.log_std = None
+        h = ctypes.c_void_p()
+        check(lib().sng_ppo_create(venv._h, ACTIVATIONS[activation], ctypes.byref(h)), venv._h)
+        self._p = h
+        venv._actors.append(weakref.ref(self))   # the env batch closes its heads with its actors, before itself
+        self._out = {}   # days -> (values, advantages, returns, log_prob)
+
+    def load(self, weights, log_std=None):
+        """Upload the value net and log_std: a dict with SB3's keys (mlp_extractor.value_net.*, value_net.*, log_std;
+        the rest is ignored), or six arrays in actor_weights' order with act_dim = 1 and log_std [act_dim] (None:
+        zeros).  They take effect at the next finish()."""
+        arrs, ls = head_weights(weights, self.obs_dim, self.act_dim, log_std)
+        if self._p is None:
+            raise RuntimeError("the PPO head is closed")
+        w = _weights_struct(arrs)
+        with torch.cuda.device(self.venv.device):
+            check(lib().sng_ppo_set_weights(self._p, ctypes.byref(w), ls.ctypes.data_as(_native.c_float_p),
+                                            _stream_handle(self.venv.device)), self.venv._h)
+        self.weights, self.log_std = arrs, ls
+        return self
+
+    def _outputs(self, days):
+        if days not in self._out:
+            T, E, dev = self.venv.timesteps, self.venv.num_envs, self.venv.device
+            # empty, not zeros: the kernel writes every element, and a fill on torch's current stream would not be
+            # ordered against a launch on a caller's stream
+            self._out[days] = (torch.empty((days, T + 1, E), dtype=torch.float32, device=dev),) + tuple(
+                torch.empty((days, T, E), dtype=torch.float32, device=dev) for _ in range(3))
+        return self._out[days]
+
+    def finish(self, obs_traj, reward_traj, done_traj, noise=None, gamma=0.99, gae_lambda=0.95, stream=None):
+        """(values [days, T + 1, E], advantages, returns, log_prob [days, T, E]) as device tensors this head owns
+        (overwritten by the next finish() of as many days), from obs_traj [days, T + 1, E, obs_dim] float32,
+        reward_traj float64 and done_traj uint8 [days, T, E] and the noise [T, E, act_dim] the actor added; without
+        noise log_prob is None.  One kernel launch on torch's current stream (or `stream`), no synchronisation."""
+        if self._p is None:
+            raise RuntimeError("the PPO head is closed")
+        venv = self.venv
+        T, E, dev = venv.timesteps, venv.num_envs, venv.device
+        days = int(obs_traj.shape[0])
+
+        def want(x, name, shape, dtype):
+            if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor {shape} on {dev}")
+        want(obs_traj, "obs_traj", (days, T + 1, E, self.obs_dim), torch.float32)
+        want(reward_traj, "reward_traj", (days, T, E), torch.float64)
+        want(done_traj, "done_traj", (days, T, E), torch.uint8)
+        if noise is not None:
+            want(noise, "noise", (T, E, self.act_dim), torch.float32)
+        values, adv, ret, logp = self._outputs(days)
+        r = _rollout_struct(days, gamma, gae_lambda, lambda x: x.data_ptr(), obs_traj, reward_traj, done_traj, noise,
+                            values, adv, ret, None if noise is None else logp)
+        s = _stream_handle(dev) if stream is None else ctypes.c_void_p(stream)
+        with torch.cuda.device(dev):
+            check(lib().sng_ppo_finish(self._p, ctypes.byref(r), s), venv._h)
+        return values, adv, ret, (None if noise is None else logp)
+
+    def host_finish(self, obs_traj, reward_traj, done_traj, noise=None, gamma=0.99, gae_lambda=0.95, values=None):
+        """The host model on numpy arrays or tensors: ppo_host_finish with this head's weights."""
+        if self.weights is None:
+            raise RuntimeError("load() the head's weights first")
+        return ppo_host_finish(_as_f32(obs_traj), _np(reward_traj), _np(done_traj), self.weights, self.log_std,
+                               None if noise is None else _as_f32(noise), gamma, gae_lambda, self.activation,
+                               None if values is None else _as_f32(values))
+
+    def close(self):
+        """Frees the head's device image.  Closing the env batch closes its heads first."""
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.venv.device)
+            lib().sng_ppo_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _np(x):
+    if torch is not None and isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
+class PpoRollout:
+    """A PPO iteration's rollout as one object: `days` closed-loop days (a ClosedLoopGraph with trajectory=True) and
+    the head's finishing kernel behind them on the same stream.  After launch() it holds what SB3's RolloutBuffer
+    holds, as device tensors: obs [days, T + 1, E, obs_dim] (obs[d, T] is the observation last_values answers),
+    actions [days, T, E, act_dim], rewards, episode_starts, advantages, returns, log_prob [days, T, E] and values
+    [days, T + 1, E].  `noise` [T, E, act_dim] is the Gaussian head's sample, reused every day, which the caller
+    fills before a launch (noise.normal_() scaled by exp(log_std)).  PPO's Gaussian head is the mean output: a
+    squashed actor or one of another net_arch is refused.  New weights (load(), or the actor's and the head's own
+    load()) take effect at the next launch, without a recapture."""
+
+    def __init__(self, venv, actor, head, days=1, gamma=0.99, gae_lambda=0.95, with_reset=True):
+        if actor.squash or actor.net_arch != (HIDDEN, HIDDEN):
+            raise ValueError("PpoRollout needs PPO's actor: 64-64 with the mean output (no squash, no other net_arch)")
+        if head.venv is not venv:
+            raise ValueError("the head was made for another env batch")
+        if head._p is None:
+            raise ValueError("the head is closed")
+        self.venv, self.actor, self.head = venv, actor, head
+        self.days, self.gamma, self.gae_lambda = int(days), float(gamma), float(gae_lambda)
+        T, E, A = venv.timesteps, venv.num_envs, venv.act_dim
+        self.noise = torch.zeros((T, E, A), dtype=torch.float32, device=venv.device)
+        self.graph = ClosedLoopGraph(venv, actor, noise=self.noise, days=self.days, with_reset=with_reset,
+                                     trajectory=True)
+        if self.graph.noise.data_ptr() != self.noise.data_ptr():   # the log-probs must be of the noise the actor adds
+            raise RuntimeError("the closed-loop graph took a copy of the noise tensor")
+        self.values = self.advantages = self.returns = self.log_prob = None
+
+    obs = property(lambda self: self.graph.obs_traj)
+    actions = property(lambda self: self.graph.action_traj)
+    rewards = property(lambda self: self.graph.reward_traj)
+    dones = property(lambda self: self.graph.done_traj)
+
+    @property
+    def episode_starts(self):
+        """uint8 [days, T, E]: 1 at a day's first step, else the done of the step before."""
+        starts = torch.ones_like(self.graph.done_traj)
+        starts[:, 1:] = self.graph.done_traj[:, :-1]
+        return starts
+
+    def load(self, state_dict):
+        """Actor, value net and log_std from one SB3 ActorCriticPolicy state_dict."""
+        self.actor.load(state_dict)
+        self.head.load(state_dict)
+        return self
+
+    def launch(self, stream=None):
+        """The graph launch and the finishing kernel, on one stream; no synchronisation."""
+        if self.head._p is None:
+            raise RuntimeError("the PPO head was closed: a PpoRollout needs it for every launch")
+        g = self.graph
+        g.launch(stream)
+        self.values, self.advantages, self.returns, self.log_prob = self.head.finish(
+            g.obs_traj, g.reward_traj, g.done_traj, self.noise, self.gamma, self.gae_lambda, stream=stream)
+
+    def close(self):
+        self.graph.close()
 
 
 class ClosedLoopGraph:
