@@ -159,7 +159,8 @@ def closed_loop_day(kw, rng, E, activation="relu", step_nodes=False, trajectory=
         g.launch()
     torch.cuda.synchronize()
     out = dict(nodes=g.step_nodes, noise=noise, ret=v.return_d.cpu().numpy(), state=v.save_state(),
-               low=v.action_space.low, high=v.action_space.high,
+               low=v.action_space.low, high=v.action_space.high, kernel=v.step_kernel_name(),
+               obs_dim=v.obs_dim, act_dim=v.act_dim,
                last=tuple(x.cpu().numpy() for x in (v.obs_d, g.actions, v.reward_d, v.done_d)))
     if trajectory:
         out.update(obs=g.obs_traj[0].cpu().numpy(), act=g.action_traj[0].cpu().numpy(),
