@@ -537,6 +537,47 @@ int sng_ppo_host_finish(int32_t obs_dim, int32_t act_dim, int32_t activation, in
                         int values_given);
 void sng_ppo_destroy(SngPpo *ppo);
 
+/* ---------------------------------------------------------------------------------------------
+ * The same for a value net of any two hidden widths: the critic of PPO("MlpPolicy", env,
+ * policy_kwargs=dict(net_arch=...)), beside an actor made by sng_policy_create_net (or the 64-64 one: SB3's
+ * dict(pi=..., vf=...) lets the two differ).
+ *
+ * The contract.  Values are SngMlpNetSpec's arithmetic with act_dim = 1, SNG_MLP_OUT_MEAN, no noise and no clip:
+ * every layer's output is the k-ordered float32 fmaf chain started from the bias over the layer's real K inputs, and V
+ * is the output layer's one chain.  Its host model is mlp_net_host (csrc/sng_policy_net_host.h) on a NetImage packed
+ * for (obs_dim, 1, hidden1, hidden2); the head's device image is that NetImage followed by log_std | inv_std as the
+ * section above lays them out (csrc/sng_ppo_net_host.h).  The device (value_net_kernel, csrc/sng_ppo_net.h, on the
+ * f32-input MFMA) may append zero-input, zero-weight terms after a chain's last real term, which can turn a -0 into
+ * +0 and nothing else, so values are compared by value (==): with relu they are equal, with tanh equal up to the
+ * device's tanhf.  GAE and the log-probability are exactly the formulas of the section above, each operation rounded
+ * on its own (gae_scan_kernel); given the stored values they are bitwise the host's.  noise [T][num_envs][act_dim] is
+ * reused every day; a NULL noise or a NULL logp skips the stage and leaves logp untouched.
+ *
+ * Refusals.  A hidden width outside 8 .. 512, or widths and an obs_dim whose LDS tiles do not fit a compute unit's
+ * 160 KB (net_spec_check's rule for act_dim = 1; the message names the sizes: every pair of widths up to 512 fits
+ * at stations of up to 50 chargers), or an act_dim above 255, is SNG_ERR_UNSUPPORTED.  A bad activation, non-finite
+ * weights or log_std, a gamma or gae_lambda outside [0, 1], days < 1 and NULL required pointers are
+ * SNG_ERR_INVALID_ARGUMENT.  In one sng_ppo_finish of a net head the days are rows of gae_scan_kernel's grid, and with
+ * the log-probability stage the T steps are T more: days (+ T with noise and logp) is at most 65535, and the
+ * days * (T + 1) * num_envs / 64 workgroups of value_net_kernel at most 2^31 - 1 (a grid's x dimension); more is
+ * SNG_ERR_INVALID_ARGUMENT with the reason.  The host entry point refuses the same specs and has no launch limits. */
+typedef struct SngPpoNetSpec {
+    int32_t hidden1, hidden2;      /* each 8 .. 512, any integer */
+    int32_t activation;            /* hidden layers: 0 tanh, 1 relu */
+} SngPpoNetSpec;
+/* A head of that value net for `env`.  SngMlpWeights holds w1 [hidden1][obs_dim], w2 [hidden2][hidden1] and
+ * w3 [1][hidden2] with their biases.  The handle that comes back is sng_ppo_create's in every other call:
+ * sng_ppo_set_weights (new weights between two sng_ppo_finish calls change the next one), sng_ppo_destroy, and
+ * sng_ppo_finish, which for a net head is two launches on `stream`, value_net_kernel then gae_scan_kernel, with no
+ * allocation and no synchronisation.  A (64, 64) net head runs these kernels too, not rollout_gae_kernel. */
+int sng_ppo_create_net(SngEnv *env, const SngPpoNetSpec *spec, SngPpo **out);
+/* Host only: the net head's contract on host arrays, as sng_ppo_host_finish is the 64-64 head's (values_given != 0:
+ * `values` is read, not computed; obs and value_net may then be NULL).  For a (64, 64) spec it gives what
+ * sng_ppo_host_finish gives.  Validates as sng_ppo_create_net, sng_ppo_set_weights and sng_ppo_finish do. */
+int sng_ppo_net_host_finish(int32_t obs_dim, int32_t act_dim, const SngPpoNetSpec *spec, int32_t T, int64_t E,
+                            const SngMlpWeights *value_net, const float *log_std,
+                            const SngPpoRollout *host_arrays, int values_given);
+
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for
  * `num_envs` envs seeded seed+i; `episode` = number of days already drawn. */

@@ -40,6 +40,7 @@
 #include "sng_policy.h"         // mlp_actor_tile, policy_kernel
 #include "sng_policy_net.h"     // policy_net_kernel
 #include "sng_ppo.h"            // rollout_gae_kernel
+#include "sng_ppo_net.h"        // value_net_kernel, gae_scan_kernel
 
 namespace sng {
 
@@ -546,6 +547,50 @@ hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoR
                : launch_kernel(rollout_gae_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs,
                                r.reward, r.done, noise, r.values, r.advantages, r.returns, r.logp, E, T, g, gl,
                                two ? 1 : 0, vec_obs, vec_noise);
+}
+
+// value_net_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises policy_net_kernel's: the same tiles,
+// above 64 KB from a hidden1 of 224 on.
+hipError_t ppo_net_kernels_init() {
+    static const hipError_t set = [] {
+        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(value_net_kernel<false>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetMaxLds);
+        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(value_net_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetMaxLds);
+        return a != hipSuccess ? a : b;
+    }();
+    return set;
+}
+
+// The two launches of a net head's sng_ppo_finish: value_net_kernel over the trajectory's rows as one flat batch, then
+// gae_scan_kernel, whose grid rows are the days and, with the log-probability stage, the T steps.
+hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRollout &r, int64_t E, int T,
+                          hipStream_t stream) {
+    const float *noise = r.logp ? r.noise : nullptr;   // no log-probability stage without both
+    const size_t lds = net_lds_bytes(m.v);
+    if (T < 1 || E < 1 || r.days < 1) return hipErrorInvalidValue;
+    const int64_t rows = ppo_net_rows(r.days, T, E), scan_rows = (int64_t)r.days + (noise ? T : 0);
+    // what ppo_net_spec_check and sng_ppo_finish refuse
+    if (lds > kNetMaxLds || m.v.N3 != kNetTile || gae_scan_lds_bytes(m.head.A) > 64u * 1024u ||
+        ppo_net_blocks(rows) > kPpoNetMaxBlocks || scan_rows > kPpoMaxLaunchDays)
+        return hipErrorInvalidValue;
+    if (lds > 64u * 1024u && ppo_net_kernels_init() != hipSuccess) return ppo_net_kernels_init();
+    const dim3 grid((unsigned)ppo_net_blocks(rows)), block(kNetBlock);
+    const hipError_t e = m.v.activation == POLICY_RELU
+                             ? launch_kernel(value_net_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img,
+                                             m.v, r.obs, r.values, rows)
+                             : launch_kernel(value_net_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img,
+                                             m.v, r.obs, r.values, rows);
+    if (e != hipSuccess) return e;
+    const dim3 sgrid((unsigned)((E + kScanBlock - 1) / kScanBlock), (unsigned)scan_rows), sblock(kScanBlock);
+    const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
+    const float *values = r.values;
+    return noise ? launch_kernel(gae_scan_kernel<true>, sgrid, sblock, gae_scan_lds_bytes(m.head.A), stream, nullptr,
+                                 nullptr, img, m.head.log_std, m.head.inv_std, (int)m.head.A, r.reward, r.done, noise,
+                                 values, r.advantages, r.returns, r.logp, E, T, (int)r.days, g, gl)
+                 : launch_kernel(gae_scan_kernel<false>, sgrid, sblock, 0, stream, nullptr, nullptr, img,
+                                 m.head.log_std, m.head.inv_std, (int)m.head.A, r.reward, r.done, noise, values,
+                                 r.advantages, r.returns, r.logp, E, T, (int)r.days, g, gl);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

@@ -8,6 +8,7 @@
 #include "sng_policy_host.h"
 #include "sng_policy_net_host.h"
 #include "sng_ppo_host.h"
+#include "sng_ppo_net_host.h"
 
 namespace sng {
 
@@ -73,6 +74,12 @@ hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoR
                               hipStream_t stream);
 // rollout_gae_kernel's dynamic-LDS limit, raised once; called by sng_ppo_create so that no capture is the first to ask.
 hipError_t ppo_kernels_init();
+// A net head's finish (sng_ppo_net.h): value_net_kernel over the days * (T + 1) * E observation rows, then
+// gae_scan_kernel; img is the device image `m` describes.  hipErrorInvalidValue for what sng_ppo_finish refuses.
+hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRollout &r, int64_t E, int T,
+                          hipStream_t stream);
+// value_net_kernel's dynamic-LDS limit, raised once; called by sng_ppo_create_net so that no capture is the first to ask.
+hipError_t ppo_net_kernels_init();
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

@@ -123,6 +123,10 @@ class SngMlpNetSpec(ctypes.Structure):
                 ("low", c_float_p), ("high", c_float_p)]
 
 
+class SngPpoNetSpec(ctypes.Structure):
+    _fields_ = [("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32), ("activation", ctypes.c_int32)]
+
+
 class SngPpoRollout(ctypes.Structure):
     _fields_ = [("days", ctypes.c_int32), ("gamma", ctypes.c_double), ("gae_lambda", ctypes.c_double),
                 ("obs", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
@@ -194,6 +198,10 @@ EXPORTS = {
                                            ctypes.c_int64, ctypes.POINTER(SngMlpWeights), c_float_p,
                                            ctypes.POINTER(SngPpoRollout), ctypes.c_int]),
     "sng_ppo_destroy": (None, [ctypes.c_void_p]),
+    "sng_ppo_create_net": (ctypes.c_int, [_H, ctypes.POINTER(SngPpoNetSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_ppo_net_host_finish": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SngPpoNetSpec),
+                                               ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(SngMlpWeights),
+                                               c_float_p, ctypes.POINTER(SngPpoRollout), ctypes.c_int]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

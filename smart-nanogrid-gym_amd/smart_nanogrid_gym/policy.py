@@ -9,8 +9,9 @@ f32-input MFMA (sng_policy_create_net), whose squashed output is SB3's DDPG / TD
 same arithmetic.  `ClosedLoopGraph` captures whole days with the actor between the steps (sng_graph_create_policy),
 so a rollout whose every action answers the observation before it is one graph launch, with no torch kernel in it.
 `PpoHead` is the rest of what a PPO update reads, in one more kernel: the critic's values, the advantages and returns
-and the log-probabilities of such a trajectory (sng_ppo_finish); `PpoRollout` is the graph and that kernel as one
-object that holds what SB3's RolloutBuffer holds.
+and the log-probabilities of such a trajectory (sng_ppo_finish); with `net_arch=` its value net has any two hidden
+widths up to 512 (sng_ppo_create_net: the value net on the f32-input MFMA over the trajectory's rows as one batch, then
+a scan kernel).  `PpoRollout` is the graph and that finish as one object that holds what SB3's RolloutBuffer holds.
 """
 import ctypes
 import weakref
@@ -256,21 +257,22 @@ class MlpActor:
             pass
 
 
-def value_weights(weights, obs_dim):
-    """The value net's six float32 arrays (w1 [64, obs_dim], b1, w2 [64, 64], b2, w3 [1, 64], b3 [1]) from six arrays
-    or tensors in that order, or from a dict holding stable-baselines3's ActorCriticPolicy keys (SB3_VALUE_KEYS);
-    other entries are ignored."""
+def value_weights(weights, obs_dim, net_arch=None):
+    """The value net's six float32 arrays (w1 [h1, obs_dim], b1, w2 [h2, h1], b2, w3 [1, h2], b3 [1]; net_arch =
+    (h1, h2), None: 64-64) from six arrays or tensors in that order, or from a dict holding stable-baselines3's
+    ActorCriticPolicy keys (SB3_VALUE_KEYS, the same for every net_arch); other entries are ignored."""
     if isinstance(weights, dict):
         missing = [k for k in SB3_VALUE_KEYS if k not in weights]
         if missing:
             raise KeyError(f"value net weights: missing {missing}")
         weights = [weights[k] for k in SB3_VALUE_KEYS]
-    return actor_weights(weights, obs_dim, 1)
+    return actor_weights(weights, obs_dim, 1, (HIDDEN, HIDDEN) if net_arch is None else net_arch)
 
 
-def head_weights(weights, obs_dim, act_dim, log_std=None):
-    """(value net arrays, log_std float32 [act_dim]) of a PPO head.  A dict gives log_std under SB3's `log_std` key
-    unless log_std is passed; with six arrays a log_std of None is zeros (SB3's log_std_init)."""
+def head_weights(weights, obs_dim, act_dim, log_std=None, net_arch=None):
+    """(value net arrays, log_std float32 [act_dim]) of a PPO head whose value net has the widths net_arch (None:
+    64-64).  A dict gives log_std under SB3's `log_std` key unless log_std is passed; with six arrays a log_std of
+    None is zeros (SB3's log_std_init)."""
     if log_std is None:
         if isinstance(weights, dict):
             if SB3_LOG_STD_KEY not in weights:
@@ -281,7 +283,7 @@ def head_weights(weights, obs_dim, act_dim, log_std=None):
     log_std = _as_f32(log_std).reshape(-1)
     if log_std.shape != (act_dim,):
         raise ValueError(f"log_std must have shape {(act_dim,)}, got {log_std.shape}")
-    return value_weights(weights, obs_dim), log_std
+    return value_weights(weights, obs_dim, net_arch), log_std
 
 
 def _rollout_struct(days, gamma, gae_lambda, ptr, obs, reward, done, noise, values, advantages, returns, logp):
@@ -291,11 +293,14 @@ def _rollout_struct(days, gamma, gae_lambda, ptr, obs, reward, done, noise, valu
 
 
 def ppo_host_finish(obs, reward, done, weights=None, log_std=None, noise=None, gamma=0.99, gae_lambda=0.95,
-                    activation="tanh", values=None):
+                    activation="tanh", values=None, net_arch=None):
     """What finishes a PPO rollout, on the CPU (sng_ppo_host_finish): (values [days, T + 1, E], advantages, returns
     [days, T, E], log_prob [days, T, E] or None without noise) for obs [days, T + 1, E, obs_dim], reward and done
     [days, T, E] and noise [T, E, act_dim].  weights / log_std: as head_weights takes them.  values: given, they are
-    read instead of computed (obs and weights may then be None).  Needs no GPU."""
+    read instead of computed (obs and weights may then be None).  net_arch: None is the 64-64 head; a pair of widths
+    is the net head's host model (sng_ppo_net_host_finish), which accepts what sng_ppo_create_net accepts.  Needs no
+    GPU."""
+    arch = None if net_arch is None else _net_arch(net_arch)
     reward = np.ascontiguousarray(reward, dtype=np.float64)
     done = np.ascontiguousarray(done, dtype=np.uint8)
     days, T, E = reward.shape
@@ -323,7 +328,7 @@ def ppo_host_finish(obs, reward, done, weights=None, log_std=None, noise=None, g
         obs_dim = 1
     w = None
     if weights is not None:
-        arrs, log_std = head_weights(weights, obs_dim, act_dim, log_std)
+        arrs, log_std = head_weights(weights, obs_dim, act_dim, log_std, arch)
         w = ctypes.byref(_weights_struct(arrs))
     else:
         log_std = np.zeros(act_dim, np.float32) if log_std is None else _as_f32(log_std).reshape(act_dim)
@@ -336,9 +341,14 @@ def ppo_host_finish(obs, reward, done, weights=None, log_std=None, noise=None, g
     adv, ret = np.zeros((days, T, E), np.float32), np.zeros((days, T, E), np.float32)
     logp = None if noise is None else np.zeros((days, T, E), np.float32)
     r = _rollout_struct(days, gamma, gae_lambda, lambda x: x.ctypes.data, obs, reward, done, noise, vals, adv, ret, logp)
-    check(lib().sng_ppo_host_finish(obs_dim, act_dim, ACTIVATIONS[activation], T, E, w,
-                                    None if log_std is None else log_std.ctypes.data_as(_native.c_float_p),
-                                    ctypes.byref(r), 1 if given else 0))
+    ls = None if log_std is None else log_std.ctypes.data_as(_native.c_float_p)
+    if arch is None:
+        check(lib().sng_ppo_host_finish(obs_dim, act_dim, ACTIVATIONS[activation], T, E, w, ls, ctypes.byref(r),
+                                        1 if given else 0))
+    else:
+        spec = _native.SngPpoNetSpec(arch[0], arch[1], ACTIVATIONS[activation])
+        check(lib().sng_ppo_net_host_finish(obs_dim, act_dim, ctypes.byref(spec), T, E, w, ls, ctypes.byref(r),
+                                            1 if given else 0))
     return vals, adv, ret, logp
 
 
@@ -346,26 +356,37 @@ class PpoHead:
     """What a PPO update reads beside the trajectory, on the device (include/sng.h, sng_ppo_create): the 64-64 value
     net of SB3's MlpPolicy with the actor's activation, the Gaussian head's log_std, and one kernel
     (rollout_gae_kernel) from a trajectory to critic values, advantages, returns and log-probabilities.  The weights
-    are zero until load()."""
+    are zero until load().
 
-    def __init__(self, venv, activation="tanh"):
+    net_arch -- None: that head.  A pair of hidden widths, each 8 .. 512 (the `vf` of SB3's net_arch): a value net of
+                those widths (sng_ppo_create_net), whose finish() is two launches: value_net_kernel on the f32-input
+                MFMA over the trajectory's days (T + 1) E rows as one batch, then gae_scan_kernel.  (64, 64) takes
+                this path too: the same results by value, for cross-checking the two.  Widths whose LDS tiles do
+                not fit a compute unit at this station are refused (NativeError, libsng error -2)."""
+
+    def __init__(self, venv, activation="tanh", net_arch=None):
         if activation not in ACTIVATIONS:
             raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
         self.venv = venv
         self.activation = activation
+        self.net_arch = None if net_arch is None else _net_arch(net_arch)
         self.obs_dim, self.act_dim = venv.obs_dim, venv.act_dim
         self.weights = self.log_std = None
         h = ctypes.c_void_p()
-        check(lib().sng_ppo_create(venv._h, ACTIVATIONS[activation], ctypes.byref(h)), venv._h)
+        if self.net_arch is None:
+            check(lib().sng_ppo_create(venv._h, ACTIVATIONS[activation], ctypes.byref(h)), venv._h)
+        else:
+            spec = _native.SngPpoNetSpec(self.net_arch[0], self.net_arch[1], ACTIVATIONS[activation])
+            check(lib().sng_ppo_create_net(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
         self._p = h
         venv._actors.append(weakref.ref(self))   # the env batch closes its heads with its actors, before itself
         self._out = {}   # days -> (values, advantages, returns, log_prob)
 
     def load(self, weights, log_std=None):
         """Upload the value net and log_std: a dict with SB3's keys (mlp_extractor.value_net.*, value_net.*, log_std;
-        the rest is ignored), or six arrays in actor_weights' order with act_dim = 1 and log_std [act_dim] (None:
-        zeros).  They take effect at the next finish()."""
-        arrs, ls = head_weights(weights, self.obs_dim, self.act_dim, log_std)
+        the rest is ignored), or six arrays in actor_weights' order with act_dim = 1 (and this head's net_arch) and
+        log_std [act_dim] (None: zeros).  They take effect at the next finish()."""
+        arrs, ls = head_weights(weights, self.obs_dim, self.act_dim, log_std, self.net_arch)
         if self._p is None:
             raise RuntimeError("the PPO head is closed")
         w = _weights_struct(arrs)
@@ -388,7 +409,8 @@ class PpoHead:
         """(values [days, T + 1, E], advantages, returns, log_prob [days, T, E]) as device tensors this head owns
         (overwritten by the next finish() of as many days), from obs_traj [days, T + 1, E, obs_dim] float32,
         reward_traj float64 and done_traj uint8 [days, T, E] and the noise [T, E, act_dim] the actor added; without
-        noise log_prob is None.  One kernel launch on torch's current stream (or `stream`), no synchronisation."""
+        noise log_prob is None.  One kernel launch (two for a head with net_arch) on torch's current stream (or
+        `stream`), no synchronisation."""
         if self._p is None:
             raise RuntimeError("the PPO head is closed")
         venv = self.venv
@@ -417,7 +439,7 @@ class PpoHead:
             raise RuntimeError("load() the head's weights first")
         return ppo_host_finish(_as_f32(obs_traj), _np(reward_traj), _np(done_traj), self.weights, self.log_std,
                                None if noise is None else _as_f32(noise), gamma, gae_lambda, self.activation,
-                               None if values is None else _as_f32(values))
+                               None if values is None else _as_f32(values), net_arch=self.net_arch)
 
     def close(self):
         """Frees the head's device image.  Closing the env batch closes its heads first."""
@@ -446,12 +468,17 @@ class PpoRollout:
     actions [days, T, E, act_dim], rewards, episode_starts, advantages, returns, log_prob [days, T, E] and values
     [days, T + 1, E].  `noise` [T, E, act_dim] is the Gaussian head's sample, reused every day, which the caller
     fills before a launch (noise.normal_() scaled by exp(log_std)).  PPO's Gaussian head is the mean output: a
-    squashed actor or one of another net_arch is refused.  New weights (load(), or the actor's and the head's own
-    load()) take effect at the next launch, without a recapture."""
+    squashed actor is refused.  With the default head the actor is 64-64 too; with a head built with net_arch= the
+    actor is any mean-output MlpActor, of any widths (SB3's net_arch=dict(pi=..., vf=...) lets the two differ).  New
+    weights (load(), or the actor's and the head's own load()) take effect at the next launch, without a recapture."""
 
     def __init__(self, venv, actor, head, days=1, gamma=0.99, gae_lambda=0.95, with_reset=True):
-        if actor.squash or actor.net_arch != (HIDDEN, HIDDEN):
-            raise ValueError("PpoRollout needs PPO's actor: 64-64 with the mean output (no squash, no other net_arch)")
+        if head.net_arch is None:
+            if actor.squash or actor.net_arch != (HIDDEN, HIDDEN):
+                raise ValueError("PpoRollout needs PPO's actor: 64-64 with the mean output (no squash, no other net_arch)")
+        elif actor.squash:
+            raise ValueError("PpoRollout needs a mean-output actor: the log-probabilities are of a = mean + noise, "
+                             "which a squashed actor (tanh, noise clipped in [-1, 1]) does not compute")
         if head.venv is not venv:
             raise ValueError("the head was made for another env batch")
         if head._p is None:
