@@ -578,6 +578,75 @@ int sng_ppo_net_host_finish(int32_t obs_dim, int32_t act_dim, const SngPpoNetSpe
                             const SngMlpWeights *value_net, const float *log_std,
                             const SngPpoRollout *host_arrays, int values_given);
 
+/* ---------------------------------------------------------------------------------------------
+ * Action noise: the exploration noise a policy graph's actor adds, drawn by the library -- the sample of PPO's
+ * Gaussian head, SB3's NormalActionNoise, and SB3's OrnsteinUhlenbeckActionNoise (DDPG: solvers/RL/ddpg_train.py:111
+ * trains with sigma = 0.5 and mean 0).  A source has one kernel (action_noise_kernel, csrc/sng_noise.h) and a host model
+ * (sng_noise_host_fill) compiled from the same text (csrc/sng_noise_host.h), which the kernel reproduces bit for bit:
+ * every operation is an integer operation, an fmaf, or a float32 add / multiply rounded on its own.
+ *
+ * Stream.  The variate of (seed, global env ge = env offset + e, action j, counter c, step t) comes from the hash
+ *     h = mix32(key + t * 0x9e3779b9u)
+ * with mix32 the device generator's ("triple32") and key a stream_key-style mix of (seed, ge, 0x6e7a0000 | j, c) in
+ * which all 64 bits of ge and of c take part (noise_key); j < 256.  So a sharded population draws what one population
+ * draws, and a block depends on nothing but its counter.
+ *
+ * Standard normal z from h, without a transcendental: sign = h >> 31, u = max(h & 0x7fffffff, 1), p = (u + 0.5) 2^-32
+ * in (0, 0.5); octave k = 30 - msb(u) (31 of them); the bits below u's leading one, left-aligned, give a 2-bit
+ * sub-segment and a 24-bit fraction x in [0, 1); r = max(fmaf(fmaf(fmaf(c3, x, c2), x, c1), x, c0), 2^-32) with the
+ * segment's four float32 coefficients from a table [31][4][4] fitted against float64 -ndtri(p) (tools/fit_noise_table.py);
+ * z = sign ? -r : r.  |z - ndtri| <= 2^-18 (measured 2.2e-6), |z| <= 6.17, z is never 0.
+ *
+ * Kinds, per action j with mu[j] and scale[j] (scale >= 0):
+ *   SNG_NOISE_GAUSSIAN   n[t] = mu[j] + scale[j] * z[t]          (PPO: scale = exp(log_std); NormalActionNoise)
+ *   SNG_NOISE_OU         x = 0 at every block's start (SB3 resets the process at an episode's end); for t = 0 .. T-1
+ *                        x = (x + ((theta * (mu[j] - x)) * dt)) + (sd[j] * z[t]),   n[t] = x,
+ *                        sd[j] = (float)(scale[j] * sqrt(dt)) formed in double at upload; theta and dt are used as
+ *                        float32 (SB3's defaults: theta 0.15, dt 1e-2).
+ *
+ * Counter.  A source owns a uint64 on the device (not the env's day counter, and not in a checkpoint blob): a fill of
+ * `days` blocks [T][num_envs][act_dim] uses counters c, c + 1, .., and a one-thread kernel behind the fill adds `days`.
+ *
+ * Refusals (SNG_ERR_INVALID_ARGUMENT, the message names the value): a kind that is neither, an act_dim outside
+ * 1 .. 255 or not the env's, non-finite mu / scale / theta / dt, a negative scale (or dt, for OU), days < 1, NULL
+ * required pointers. */
+#define SNG_NOISE_GAUSSIAN 0
+#define SNG_NOISE_OU       1
+typedef struct SngNoiseSpec {
+    int32_t kind;                   /* SNG_NOISE_* */
+    int32_t act_dim;                /* the env's, 1 .. 255 */
+    uint64_t seed;
+    double theta, dt;               /* SNG_NOISE_OU; finite for both kinds */
+} SngNoiseSpec;
+typedef struct SngNoise SngNoise;
+
+/* A source for `env` (its act_dim, T and num_envs), counter 0, mu and scale zero until sng_noise_set_params.  Destroyed
+ * before its env and after the graphs created with it. */
+int sng_noise_create(SngEnv *env, const SngNoiseSpec *spec, SngNoise **out);
+/* Upload mu (host [act_dim], or NULL for zeros) and scale (host [act_dim]), asynchronously on `stream`: fills and
+ * captured graphs read the uploaded image, so new values between two launches change the next launch without a
+ * recapture, as weights do. */
+int sng_noise_set_params(SngNoise *noise, const float *mu, const float *scale, void *stream);
+/* `days` blocks into out (device [days][T][num_envs][act_dim] f32): the fill launch and the counter's bump, asynchronous
+ * on `stream`, with no allocation and no synchronisation.  The env offset is read when the call is enqueued. */
+int sng_noise_fill(SngNoise *noise, float *out, int32_t days, void *stream);
+/* The counter the next fill starts from, for checkpoints; both synchronise `stream`. */
+int sng_noise_get_counter(SngNoise *noise, uint64_t *out, void *stream);
+int sng_noise_set_counter(SngNoise *noise, uint64_t counter, void *stream);
+void sng_noise_destroy(SngNoise *noise);
+/* Host only: the blocks a source with this spec, mu (NULL: zeros) and scale gives envs env_offset .. env_offset + E - 1
+ * from `counter` on, into out (host [days][T][E][act_dim]).  Validates as the device calls do. */
+int sng_noise_host_fill(const SngNoiseSpec *spec, const float *mu, const float *scale, int32_t T, int64_t E,
+                        int64_t env_offset, uint64_t counter, int32_t days, float *out);
+/* sng_graph_create_policy with a source in the place of the caller's noise: the graph's first nodes are one fill of all
+ * `days` blocks into noise_out (device [days][T][num_envs][act_dim]) and the counter's bump, on the serial chain, and
+ * day d's actor reads block d -- in the node form and in the fused form alike -- so every day explores with its own
+ * sample and every replay draws new days.  Everything else is sng_graph_create_policy's, whose own one-block behaviour
+ * is unchanged. */
+int sng_graph_create_policy_noise(SngEnv *env, SngPolicy *policy, SngNoise *noise_source, float *noise_out, float *obs,
+                                  float *actions_out, double *reward, uint8_t *done, const SngInfo *info, int flags,
+                                  int32_t days, double *day_returns, SngGraph **out);
+
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for
  * `num_envs` envs seeded seed+i; `episode` = number of days already drawn. */

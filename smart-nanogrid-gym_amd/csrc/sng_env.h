@@ -94,6 +94,17 @@ struct SngPolicy {
     hipEvent_t uploaded = nullptr;            // the last upload has read h_img
 };
 
+// An action-noise source of a handle's envs (sng_noise.cpp): the spec, the per-action parameters' device image
+// (sng_noise_host.h, noise_pack_params: mu [A], sd [A]) with its pinned mirror, and the counter of the next block, on
+// the device, which only the kernel behind a fill advances.
+struct SngNoise {
+    SngEnv *env = nullptr;
+    SngNoiseSpec spec{};
+    float *d_params = nullptr, *h_params = nullptr;
+    uint64_t *d_counter = nullptr;
+    hipEvent_t uploaded = nullptr;   // the last upload has read h_params
+};
+
 struct SngGraph {
     SngEnv *env = nullptr;
     SngPolicy *policy = nullptr;   // sng_graph_create_policy: the actor between the steps

@@ -24,9 +24,11 @@ static hipError_t launch_actor(const SngPolicy *policy, const float *obs, const 
 // one (sng_policy.cpp), every step's actions are the actor's answer to the observation before it: `noise` (T
 // blocks, may be null) takes the place of the actions stream, `actions_out` receives a, and the step nodes read the
 // policy's clipped actions.
+// With a noise source (sng_graph_create_policy_noise), `noise` is the [days][T][E][A] buffer the graph's first node fills
+// and day d's actor reads block d of; without one it is the caller's one block, read every day.
 static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, const float *noise, float *actions_out,
                         float *obs, double *reward, uint8_t *done, const SngInfo *info, int flags, int32_t days,
-                        double *day_returns, SngGraph **out) {
+                        double *day_returns, SngGraph **out, SngNoise *noise_source = nullptr) {
     const bool with_reset = (flags & SNG_GRAPH_RESET) != 0;
     if (policy) actions = policy->d_env_actions;
     if (!env || !actions || !obs || !reward || !done || !out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
@@ -111,6 +113,11 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
     };
     if (e == hipSuccess) e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     const bool capturing = e == hipSuccess;
+    // a source's fill of every day's block and its counter's bump: the chain's first nodes
+    const size_t noise_day = noise_source ? (size_t)p.T * (size_t)E * (size_t)A : 0;
+    if (noise_source && e == hipSuccess)
+        e = launch_noise_fill(noise_source->spec, noise_source->d_params, noise_source->d_counter, p.env_offset,
+                              const_cast<float *>(noise), days, p.T, E, cs);
     if (g->overlapped && e == hipSuccess) {   // fork
         e = hipEventRecord(stepped[0], cs);
         if (e == hipSuccess) e = hipStreamWaitEvent(gs, stepped[0], 0);
@@ -137,14 +144,15 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
             // step t answers the observation in block t of the day (the reset's, then step t - 1's)
             const size_t act_block = (size_t)E * (size_t)A;
             float *a_d = actions_out + (traj ? (size_t)d * (size_t)p.T * act_block : 0);
+            const float *noise_d = noise ? noise + (size_t)d * noise_day : nullptr;
             if (e == hipSuccess && g->day_kernel)
-                e = launch_policy_day(pd, ds, ipd, policy->d_img, policy->image, noise, obs0, obs_d, a_d, reward_d, done_d,
+                e = launch_policy_day(pd, ds, ipd, policy->d_img, policy->image, noise_d, obs0, obs_d, a_d, reward_d, done_d,
                                       E, (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step,
                                       traj ? (int64_t)act_block : 0);
             for (int t = 0; e == hipSuccess && !g->day_kernel && t < p.T; ++t) {
                 float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
                 e = launch_actor(policy, obs0 + (size_t)t * (size_t)obs_step,
-                                 noise ? noise + (size_t)t * act_block : nullptr, a_d + (traj ? (size_t)t * act_block : 0),
+                                 noise_d ? noise_d + (size_t)t * act_block : nullptr, a_d + (traj ? (size_t)t * act_block : 0),
                                  policy->d_env_actions, E, cs);
                 if (e == hipSuccess)
                     e = launch_step(pd, ds, ipd, env->host_tab, policy->d_env_actions, obs_t,
@@ -207,6 +215,17 @@ int sng_graph_create_policy(SngEnv *env, SngPolicy *policy, const float *noise, 
     if (!env || !policy || !actions_out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
     if (policy->env != env) return fail(env, SNG_ERR_INVALID_ARGUMENT, "the policy was created for another env");
     return capture_days(env, policy, nullptr, noise, actions_out, obs, reward, done, info, flags, days, day_returns, out);
+}
+
+int sng_graph_create_policy_noise(SngEnv *env, SngPolicy *policy, SngNoise *noise_source, float *noise_out, float *obs,
+                                  float *actions_out, double *reward, uint8_t *done, const SngInfo *info, int flags,
+                                  int32_t days, double *day_returns, SngGraph **out) {
+    if (!env || !policy || !actions_out || !noise_source || !noise_out)
+        return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
+    if (policy->env != env) return fail(env, SNG_ERR_INVALID_ARGUMENT, "the policy was created for another env");
+    if (noise_source->env != env) return fail(env, SNG_ERR_INVALID_ARGUMENT, "the noise source was created for another env");
+    return capture_days(env, policy, nullptr, noise_out, actions_out, obs, reward, done, info, flags, days, day_returns, out,
+                        noise_source);
 }
 
 int sng_graph_launch(SngGraph *g, void *stream) {

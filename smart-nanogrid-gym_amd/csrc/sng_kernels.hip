@@ -41,6 +41,7 @@
 #include "sng_policy_net.h"     // policy_net_kernel
 #include "sng_ppo.h"            // rollout_gae_kernel
 #include "sng_ppo_net.h"        // value_net_kernel, gae_scan_kernel
+#include "sng_noise.h"          // action_noise_kernel
 
 namespace sng {
 
@@ -591,6 +592,28 @@ hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRo
                  : launch_kernel(gae_scan_kernel<false>, sgrid, sblock, 0, stream, nullptr, nullptr, img,
                                  m.head.log_std, m.head.inv_std, (int)m.head.A, r.reward, r.done, noise, values,
                                  r.advantages, r.returns, r.logp, E, T, (int)r.days, g, gl);
+}
+
+// A source's fill and, behind it, its counter's bump: grid x over the row's groups of four elements, y over the blocks.
+hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint64_t *counter, int64_t env_offset,
+                             float *out, int32_t days, int T, int64_t E, hipStream_t stream) {
+    const int A = spec.act_dim;
+    if (days < 1 || T < 1 || E < 1 || A < 1 || A > kNoiseMaxAct || !params || !counter || !out) return hipErrorInvalidValue;
+    const int64_t row = E * (int64_t)A, per = (int64_t)kNoiseBlock * kNoisePer;
+    const int64_t blocks = (row + per - 1) / per;
+    if (blocks > 2147483647ll) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks, (unsigned)(days < kNoiseMaxGridDays ? days : kNoiseMaxGridDays)), block(kNoiseBlock);
+    const int vec = (((uintptr_t)out & 15u) == 0 && row % 4 == 0) ? 1 : 0;
+    const float theta = (float)spec.theta, dt = (float)spec.dt;
+    const hipError_t e =
+        spec.kind == SNG_NOISE_OU
+            ? launch_kernel(action_noise_kernel<SNG_NOISE_OU>, grid, block, 0, stream, nullptr, nullptr, params,
+                            (const uint64_t *)counter, spec.seed, env_offset, theta, dt, out, (int)days, T, E, A, vec)
+            : launch_kernel(action_noise_kernel<SNG_NOISE_GAUSSIAN>, grid, block, 0, stream, nullptr, nullptr, params,
+                            (const uint64_t *)counter, spec.seed, env_offset, theta, dt, out, (int)days, T, E, A, vec);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(noise_bump_kernel, dim3(1), dim3(1), 0, stream, counter, (uint64_t)days);
+    return hipGetLastError();
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

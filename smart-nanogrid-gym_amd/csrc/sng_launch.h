@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sng_layout.h"
+#include "sng_noise_host.h"
 #include "sng_policy_host.h"
 #include "sng_policy_net_host.h"
 #include "sng_ppo_host.h"
@@ -80,6 +81,11 @@ hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRo
                           hipStream_t stream);
 // value_net_kernel's dynamic-LDS limit, raised once; called by sng_ppo_create_net so that no capture is the first to ask.
 hipError_t ppo_net_kernels_init();
+// A noise source's fill (sng_noise.h, action_noise_kernel) of `days` blocks [T][E][act_dim] into out, from the counter's
+// value on, and the one-thread kernel that adds `days` to the counter behind it; params is the device image
+// noise_pack_params fills.
+hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint64_t *counter, int64_t env_offset,
+                             float *out, int32_t days, int T, int64_t E, hipStream_t stream);
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

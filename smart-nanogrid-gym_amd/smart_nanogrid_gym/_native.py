@@ -134,6 +134,15 @@ class SngPpoRollout(ctypes.Structure):
                 ("returns", ctypes.c_void_p), ("logp", ctypes.c_void_p)]
 
 
+NOISE_GAUSSIAN = 0   # sng.h SNG_NOISE_GAUSSIAN
+NOISE_OU = 1         # sng.h SNG_NOISE_OU
+
+
+class SngNoiseSpec(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("theta", ctypes.c_double), ("dt", ctypes.c_double)]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -202,6 +211,18 @@ EXPORTS = {
     "sng_ppo_net_host_finish": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SngPpoNetSpec),
                                                ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(SngMlpWeights),
                                                c_float_p, ctypes.POINTER(SngPpoRollout), ctypes.c_int]),
+    "sng_noise_create": (ctypes.c_int, [_H, ctypes.POINTER(SngNoiseSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_noise_set_params": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, _S]),
+    "sng_noise_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, _S]),
+    "sng_noise_get_counter": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), _S]),
+    "sng_noise_set_counter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, _S]),
+    "sng_noise_destroy": (None, [ctypes.c_void_p]),
+    "sng_noise_host_fill": (ctypes.c_int, [ctypes.POINTER(SngNoiseSpec), c_float_p, c_float_p, ctypes.c_int32,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32, c_float_p]),
+    "sng_graph_create_policy_noise": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.POINTER(SngInfo), ctypes.c_int, ctypes.c_int32,
+                                                     ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

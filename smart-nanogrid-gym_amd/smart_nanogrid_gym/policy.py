@@ -12,6 +12,8 @@ so a rollout whose every action answers the observation before it is one graph l
 and the log-probabilities of such a trajectory (sng_ppo_finish); with `net_arch=` its value net has any two hidden
 widths up to 512 (sng_ppo_create_net: the value net on the f32-input MFMA over the trajectory's rows as one batch, then
 a scan kernel).  `PpoRollout` is the graph and that finish as one object that holds what SB3's RolloutBuffer holds.
+`ActionNoise` is the exploration noise those graphs add, drawn by the library (sng_noise_create): Gaussian or
+Ornstein-Uhlenbeck blocks from counter-based streams with an exact host model, a new block per day and per launch.
 """
 import ctypes
 import weakref
@@ -461,18 +463,154 @@ def _np(x):
     return np.asarray(x)
 
 
+NOISE_KINDS = {"gaussian": _native.NOISE_GAUSSIAN, "ou": _native.NOISE_OU}
+
+
+def _per_action(x, act_dim, name):
+    x = _as_f32(x)
+    if x.ndim > 1 or (x.ndim == 1 and x.shape[0] not in (1, act_dim)):
+        raise ValueError(f"{name} must be a scalar or have shape {(act_dim,)}, got {x.shape}")
+    return np.ascontiguousarray(np.broadcast_to(x, (act_dim,)))
+
+
+def _noise_spec(kind, act_dim, seed, theta, dt):
+    if kind not in NOISE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(NOISE_KINDS)}")
+    return _native.SngNoiseSpec(NOISE_KINDS[kind], int(act_dim), int(seed), float(theta), float(dt))
+
+
+def noise_host_fill(kind, act_dim, timesteps, num_envs, days=1, seed=0, mu=0.0, scale=1.0, theta=0.15, dt=1e-2,
+                    env_offset=0, counter=0):
+    """The action noise's host model (sng_noise_host_fill): float32 [days, timesteps, num_envs, act_dim], the blocks
+    of counters counter, counter + 1, .. that an ActionNoise with these parameters gives the global envs env_offset ..
+    env_offset + num_envs - 1.  mu and scale: scalars or [act_dim].  Needs no GPU."""
+    spec = _noise_spec(kind, act_dim, seed, theta, dt)
+    A = max(int(act_dim), 1)
+    mu, scale = _per_action(mu, A, "mu"), _per_action(scale, A, "scale")
+    out = np.zeros((max(int(days), 0), max(int(timesteps), 0), max(int(num_envs), 0), A), np.float32)
+    F = _native.c_float_p
+    check(lib().sng_noise_host_fill(ctypes.byref(spec), mu.ctypes.data_as(F), scale.ctypes.data_as(F), int(timesteps),
+                                    int(num_envs), int(env_offset), int(counter), int(days), out.ctypes.data_as(F)))
+    return out
+
+
+class ActionNoise:
+    """The exploration noise of `venv`'s envs, drawn on the device (include/sng.h, sng_noise_create): one kernel fills
+    whole days' blocks [T, E, act_dim] from counter-based streams keyed by (seed, global env, action, counter, step), so
+    a sharded population draws what one population draws, every block has an exact CPU model (host_fill), and a
+    captured graph (ClosedLoopGraph(noise=source), PpoRollout(noise=source)) explores with a new sample every day
+    and every replay.
+
+    kind  -- "gaussian": n = mu + scale * z, PPO's sample with scale = exp(log_std) and SB3's NormalActionNoise(mean,
+             sigma); "ou": SB3's OrnsteinUhlenbeckActionNoise(mean, sigma, theta, dt), restarted from 0 every day
+    seed  -- of the streams; the source's own, apart from the env's
+    mu, scale -- scalars or [act_dim]; set() replaces them, also between two launches of a captured graph
+    theta, dt -- of the OU process (SB3's defaults)
+    `counter` is the number of blocks drawn so far: the next fill starts there.  Reading or setting it synchronises."""
+
+    def __init__(self, venv, kind="gaussian", seed=0, mu=0.0, scale=1.0, theta=0.15, dt=1e-2):
+        self.venv, self.kind, self.seed = venv, kind, int(seed)
+        self.theta, self.dt = float(theta), float(dt)
+        self.act_dim = venv.act_dim
+        self._spec = _noise_spec(kind, self.act_dim, seed, theta, dt)
+        self._p = None
+        h = ctypes.c_void_p()
+        with torch.cuda.device(venv.device):
+            check(lib().sng_noise_create(venv._h, ctypes.byref(self._spec), ctypes.byref(h)), venv._h)
+        self._p = h
+        venv._actors.append(weakref.ref(self))   # the env batch closes its sources with its actors, before itself
+        self._out = {}   # days -> tensor
+        self.mu = self.scale = None
+        self.set(mu, scale)
+
+    def set(self, mu, scale):
+        """Upload new per-action mu and scale (scalars or [act_dim]); they take effect at the next fill or launch."""
+        if self._p is None:
+            raise RuntimeError("the noise source is closed")
+        mu, scale = _per_action(mu, self.act_dim, "mu"), _per_action(scale, self.act_dim, "scale")
+        F = _native.c_float_p
+        with torch.cuda.device(self.venv.device):
+            check(lib().sng_noise_set_params(self._p, mu.ctypes.data_as(F), scale.ctypes.data_as(F),
+                                             _stream_handle(self.venv.device)), self.venv._h)
+        self.mu, self.scale = mu, scale
+        return self
+
+    def fill(self, days=1, out=None, stream=None):
+        """`days` new blocks as a device tensor [days, T, E, act_dim] this source owns (overwritten by the next fill
+        of as many days), or into `out`; two launches on torch's current stream (or `stream`), no synchronisation."""
+        if self._p is None:
+            raise RuntimeError("the noise source is closed")
+        venv = self.venv
+        shape = (int(days), venv.timesteps, venv.num_envs, self.act_dim)
+        if out is None:
+            if days not in self._out and int(days) >= 1:
+                self._out[days] = torch.empty(shape, dtype=torch.float32, device=venv.device)
+            out = self._out.get(days)
+        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != venv.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor {shape} on {venv.device}")
+        s = _stream_handle(venv.device) if stream is None else ctypes.c_void_p(stream)
+        with torch.cuda.device(venv.device):
+            check(lib().sng_noise_fill(self._p, None if out is None else ctypes.c_void_p(out.data_ptr()), int(days), s),
+                  venv._h)
+        return out
+
+    def host_fill(self, days=1, counter=None):
+        """The host model of the blocks a fill of `days` gives from `counter` on (None: the source's current counter)
+        with the current mu and scale: numpy float32 [days, T, E, act_dim]."""
+        venv = self.venv
+        return noise_host_fill(self.kind, self.act_dim, venv.timesteps, venv.num_envs, days, self.seed, self.mu,
+                               self.scale, self.theta, self.dt, venv.env_offset,
+                               self.counter if counter is None else counter)
+
+    @property
+    def counter(self):
+        if self._p is None:
+            raise RuntimeError("the noise source is closed")
+        c = ctypes.c_uint64()
+        with torch.cuda.device(self.venv.device):
+            check(lib().sng_noise_get_counter(self._p, ctypes.byref(c), _stream_handle(self.venv.device)), self.venv._h)
+        return int(c.value)
+
+    @counter.setter
+    def counter(self, value):
+        if self._p is None:
+            raise RuntimeError("the noise source is closed")
+        with torch.cuda.device(self.venv.device):
+            check(lib().sng_noise_set_counter(self._p, int(value), _stream_handle(self.venv.device)), self.venv._h)
+
+    def close(self):
+        """Frees the source's device buffers.  Closing the env batch closes its sources first; graphs captured with
+        the source must not be launched afterwards."""
+        if getattr(self, "_p", None):
+            torch.cuda.synchronize(self.venv.device)
+            lib().sng_noise_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PpoRollout:
     """A PPO iteration's rollout as one object: `days` closed-loop days (a ClosedLoopGraph with trajectory=True) and
     the head's finishing kernel behind them on the same stream.  After launch() it holds what SB3's RolloutBuffer
     holds, as device tensors: obs [days, T + 1, E, obs_dim] (obs[d, T] is the observation last_values answers),
     actions [days, T, E, act_dim], rewards, episode_starts, advantages, returns, log_prob [days, T, E] and values
     [days, T + 1, E].  `noise` [T, E, act_dim] is the Gaussian head's sample, reused every day, which the caller
-    fills before a launch (noise.normal_() scaled by exp(log_std)).  PPO's Gaussian head is the mean output: a
+    fills before a launch (noise.normal_() scaled by exp(log_std)).  With noise=<a gaussian ActionNoise> the library
+    draws it instead: `noise` is then [days, T, E, act_dim], one block per day, new at every launch; load() also sets
+    the source's scale to exp(log_std) (numpy float32); launch() runs the graph and one finish per day on that day's
+    blocks, so log_prob[d] is of day d's own noise.  PPO's Gaussian head is the mean output: a
     squashed actor is refused.  With the default head the actor is 64-64 too; with a head built with net_arch= the
     actor is any mean-output MlpActor, of any widths (SB3's net_arch=dict(pi=..., vf=...) lets the two differ).  New
     weights (load(), or the actor's and the head's own load()) take effect at the next launch, without a recapture."""
 
-    def __init__(self, venv, actor, head, days=1, gamma=0.99, gae_lambda=0.95, with_reset=True):
+    def __init__(self, venv, actor, head, days=1, gamma=0.99, gae_lambda=0.95, with_reset=True, noise=None):
+        if noise is not None and (not isinstance(noise, ActionNoise) or noise.kind != "gaussian"):
+            raise ValueError("PpoRollout's noise is None (the caller fills `noise`) or a gaussian ActionNoise")
         if head.net_arch is None:
             if actor.squash or actor.net_arch != (HIDDEN, HIDDEN):
                 raise ValueError("PpoRollout needs PPO's actor: 64-64 with the mean output (no squash, no other net_arch)")
@@ -486,11 +624,17 @@ class PpoRollout:
         self.venv, self.actor, self.head = venv, actor, head
         self.days, self.gamma, self.gae_lambda = int(days), float(gamma), float(gae_lambda)
         T, E, A = venv.timesteps, venv.num_envs, venv.act_dim
-        self.noise = torch.zeros((T, E, A), dtype=torch.float32, device=venv.device)
-        self.graph = ClosedLoopGraph(venv, actor, noise=self.noise, days=self.days, with_reset=with_reset,
-                                     trajectory=True)
-        if self.graph.noise.data_ptr() != self.noise.data_ptr():   # the log-probs must be of the noise the actor adds
-            raise RuntimeError("the closed-loop graph took a copy of the noise tensor")
+        self.noise_source = noise
+        if noise is None:
+            self.noise = torch.zeros((T, E, A), dtype=torch.float32, device=venv.device)
+            self.graph = ClosedLoopGraph(venv, actor, noise=self.noise, days=self.days, with_reset=with_reset,
+                                         trajectory=True)
+            if self.graph.noise.data_ptr() != self.noise.data_ptr():   # the log-probs must be of the noise the actor adds
+                raise RuntimeError("the closed-loop graph took a copy of the noise tensor")
+        else:   # the source's blocks, one per day: [days, T, E, A]
+            self.graph = ClosedLoopGraph(venv, actor, noise=noise, days=self.days, with_reset=with_reset, trajectory=True)
+            self.noise = self.graph.noise_traj
+            self._day_out = None
         self.values = self.advantages = self.returns = self.log_prob = None
 
     obs = property(lambda self: self.graph.obs_traj)
@@ -509,6 +653,8 @@ class PpoRollout:
         """Actor, value net and log_std from one SB3 ActorCriticPolicy state_dict."""
         self.actor.load(state_dict)
         self.head.load(state_dict)
+        if self.noise_source is not None:   # the Gaussian head's sample: scale = exp(log_std), in float32
+            self.noise_source.set(self.noise_source.mu, np.exp(self.head.log_std.astype(np.float32)).astype(np.float32))
         return self
 
     def launch(self, stream=None):
@@ -517,8 +663,25 @@ class PpoRollout:
             raise RuntimeError("the PPO head was closed: a PpoRollout needs it for every launch")
         g = self.graph
         g.launch(stream)
-        self.values, self.advantages, self.returns, self.log_prob = self.head.finish(
-            g.obs_traj, g.reward_traj, g.done_traj, self.noise, self.gamma, self.gae_lambda, stream=stream)
+        if self.noise_source is None:
+            self.values, self.advantages, self.returns, self.log_prob = self.head.finish(
+                g.obs_traj, g.reward_traj, g.done_traj, self.noise, self.gamma, self.gae_lambda, stream=stream)
+            return
+        # one finish per day (sng_ppo_finish with days = 1), on that day's blocks and that day's noise, straight into
+        # day d's rows of this object's [days, ..] outputs
+        venv = self.venv
+        if self._day_out is None:
+            T, E, dev = venv.timesteps, venv.num_envs, venv.device
+            self._day_out = (torch.empty((self.days, T + 1, E), dtype=torch.float32, device=dev),) + tuple(
+                torch.empty((self.days, T, E), dtype=torch.float32, device=dev) for _ in range(3))
+        vals, adv, ret, logp = self._day_out
+        s = _stream_handle(venv.device) if stream is None else ctypes.c_void_p(stream)
+        with torch.cuda.device(venv.device):
+            for d in range(self.days):
+                r = _rollout_struct(1, self.gamma, self.gae_lambda, lambda x: x.data_ptr(), g.obs_traj[d],
+                                    g.reward_traj[d], g.done_traj[d], self.noise[d], vals[d], adv[d], ret[d], logp[d])
+                check(lib().sng_ppo_finish(self.head._p, ctypes.byref(r), s), venv._h)
+        self.values, self.advantages, self.returns, self.log_prob = vals, adv, ret, logp
 
     def close(self):
         self.graph.close()
@@ -529,7 +692,10 @@ class ClosedLoopGraph:
     (actor, step)) x days (include/sng.h, sng_graph_create_policy).
 
     noise      -- optional device tensor [T, E, act_dim] added to the actor's mean (to tanh(mean) for a squashed
-                  actor: DDPG's action noise, e.g. a precomputed Ornstein-Uhlenbeck path), reused every day
+                  actor: DDPG's action noise, e.g. a precomputed Ornstein-Uhlenbeck path), reused every day; or an
+                  ActionNoise: the graph then begins with the source's fill of noise_traj [days, T, E, act_dim]
+                  (sng_graph_create_policy_noise), day d's actor reads noise_traj[d], and every launch draws new
+                  blocks
     trajectory -- True: keeps every step: obs_traj [days, T + 1, E, obs_dim], action_traj [days, T, E, act_dim] (a,
                   before the clip or the rescale), reward_traj and done_traj [days, T, E]; obs_traj[d, t] is the
                   observation action_traj[d, t] answered.  False: venv.obs_d / reward_d / done_d and `actions`
@@ -557,8 +723,15 @@ class ClosedLoopGraph:
         self.with_reset = bool(with_reset)
         self.trajectory = bool(trajectory)
         T, E, A = venv.timesteps, venv.num_envs, venv.act_dim
-        self.noise = None
-        if noise is not None:
+        self.noise = self.noise_source = self.noise_traj = None
+        if isinstance(noise, ActionNoise):
+            if noise.venv is not venv:
+                raise ValueError("the noise source was made for another env batch")
+            if noise._p is None:
+                raise ValueError("the noise source is closed")
+            self.noise_source = noise
+            self.noise_traj = torch.zeros((self.days, T, E, A), dtype=torch.float32, device=venv.device)
+        elif noise is not None:
             self.noise = noise.to(device=venv.device, dtype=torch.float32).contiguous()
             if tuple(self.noise.shape) != (T, E, A):
                 raise ValueError(f"noise must have shape {(T, E, A)}")
@@ -582,14 +755,18 @@ class ClosedLoopGraph:
             self.actions = torch.zeros((E, A), dtype=torch.float32, device=venv.device)
         out = self.action_traj if self.trajectory else self.actions
         g = ctypes.c_void_p()
+        flags = ((_native.GRAPH_RESET if with_reset else 0) | (_native.GRAPH_STEP_NODES if step_nodes else 0)
+                 | (_native.GRAPH_TRAJECTORY if self.trajectory else 0) | (_native.GRAPH_POLICY_FUSED if fused else 0))
+        rest = (ctypes.c_void_p(obs.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(reward.data_ptr()),
+                ctypes.c_void_p(done.data_ptr()), ctypes.byref(venv._info), flags, self.days, dr, ctypes.byref(g))
         with torch.cuda.device(venv.device):
-            check(lib().sng_graph_create_policy(
-                venv._h, actor._p, None if self.noise is None else ctypes.c_void_p(self.noise.data_ptr()),
-                ctypes.c_void_p(obs.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(reward.data_ptr()),
-                ctypes.c_void_p(done.data_ptr()), ctypes.byref(venv._info),
-                (_native.GRAPH_RESET if with_reset else 0) | (_native.GRAPH_STEP_NODES if step_nodes else 0)
-                | (_native.GRAPH_TRAJECTORY if self.trajectory else 0)
-                | (_native.GRAPH_POLICY_FUSED if fused else 0), self.days, dr, ctypes.byref(g)), venv._h)
+            if self.noise_source is not None:
+                check(lib().sng_graph_create_policy_noise(venv._h, actor._p, self.noise_source._p,
+                                                          ctypes.c_void_p(self.noise_traj.data_ptr()), *rest), venv._h)
+            else:
+                check(lib().sng_graph_create_policy(
+                    venv._h, actor._p, None if self.noise is None else ctypes.c_void_p(self.noise.data_ptr()), *rest),
+                    venv._h)
         self._g = g
 
     @property
@@ -601,6 +778,8 @@ class ClosedLoopGraph:
     def launch(self, stream=None):
         if self.actor._p is None:   # the graph reads the actor's device image and its clipped-actions block
             raise RuntimeError("the actor was closed: a ClosedLoopGraph needs it for every launch")
+        if self.noise_source is not None and self.noise_source._p is None:   # ... and the source's counter
+            raise RuntimeError("the noise source was closed: a ClosedLoopGraph needs it for every launch")
         s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)
         if self.trajectory and not self.with_reset:   # the loaded day's t = 0 observation, ahead of the graph
             if stream is None:
