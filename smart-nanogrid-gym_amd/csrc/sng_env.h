@@ -76,33 +76,74 @@ struct SngEnv {
     size_t timeline() const { return (size_t)p.T * p.n * (size_t)E; }
 };
 
-// An MLP actor of a handle's envs (sng_policy.cpp): the spec, the device image the policy kernels and the graphs
-// captured with it read (sng_policy_host.h, PolicyImage), its pinned host mirror, which sng_policy_set_weights packs
-// and uploads from, and the clipped actions a captured step node reads.
+// A device image with its pinned host mirror and the event of its last upload: what a handle keeps whose parameters
+// are packed on the host and uploaded on a caller's stream (SngPolicy, SngPpo, SngNoise).
+struct UploadedImage {
+    float *d = nullptr, *h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t uploaded = nullptr;   // the last upload has read h
+
+    hipError_t create(size_t n) {
+        bytes = n;
+        hipError_t e = hipMalloc((void **)&d, n);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&h, n, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&uploaded, hipEventDisableTiming);
+        return e;
+    }
+    // pack(h) fills the mirror once the upload before this one has read it; then the copy and its event on `st`
+    template <class Pack>
+    hipError_t upload(hipStream_t st, Pack pack) {
+        hipError_t e = hipEventSynchronize(uploaded);
+        if (e != hipSuccess) return e;
+        pack(h);
+        e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
+        return e != hipSuccess ? e : hipEventRecord(uploaded, st);
+    }
+    // a new handle's first image: uploaded, and on the device when this returns
+    template <class Pack>
+    hipError_t upload_now(Pack pack) {
+        const hipError_t e = upload(nullptr, pack);
+        return e != hipSuccess ? e : hipEventSynchronize(uploaded);
+    }
+    void destroy() {
+        if (uploaded) {
+            (void)hipEventSynchronize(uploaded);
+            (void)hipEventDestroy(uploaded);
+        }
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        uploaded = nullptr;
+    }
+};
+
+// An MLP actor of a handle's envs (sng_policy.cpp): the device image the policy kernels and the graphs captured with
+// it read, which sng_policy_set_weights packs and uploads, and the clipped actions a captured step node reads.  It has
+// one of two forms: sng_policy_create's 64-64 actor (spec, image: sng_policy_host.h) or, with `net`,
+// sng_policy_create_net's actor of any width (net_spec, net_image: sng_policy_net_host.h).  What depends on the form
+// is decided in policy_weights_ok, policy_pack_image, launch_actor and policy_graph_fused below, and nowhere else.
 struct SngPolicy {
     SngEnv *env = nullptr;
-    SngMlpSpec spec{};
-    std::vector<float> clip_low, clip_high;   // owned copies behind spec.clip_low / clip_high
-    sng::PolicyImage image{};
-    // sng_policy_create_net: the net's spec and image (sng_policy_net_host.h) in the place of spec and image; its
-    // bounds are kept in clip_low / clip_high too
     bool net = false;
+    int O = 0, A = 0, H1 = 0, H2 = 0;   // the dims, whichever the form
+    size_t floats = 0;                  // of the image
+    SngMlpSpec spec{};
+    sng::PolicyImage image{};
     SngMlpNetSpec net_spec{};
     sng::NetImage net_image{};
-    float *d_img = nullptr, *h_img = nullptr;
+    std::vector<float> clip_low, clip_high;   // owned copies behind the spec's bounds
+    UploadedImage img;
     float *d_env_actions = nullptr;           // [E][act_dim]
-    hipEvent_t uploaded = nullptr;            // the last upload has read h_img
 };
 
 // An action-noise source of a handle's envs (sng_noise.cpp): the spec, the per-action parameters' device image
-// (sng_noise_host.h, noise_pack_params: mu [A], sd [A]) with its pinned mirror, and the counter of the next block, on
-// the device, which only the kernel behind a fill advances.
+// (sng_noise_host.h, noise_pack_params: mu [A], sd [A]), and the counter of the next block, on the device, which only
+// the kernel behind a fill advances.
 struct SngNoise {
     SngEnv *env = nullptr;
     SngNoiseSpec spec{};
-    float *d_params = nullptr, *h_params = nullptr;
+    UploadedImage params;
     uint64_t *d_counter = nullptr;
-    hipEvent_t uploaded = nullptr;   // the last upload has read h_params
 };
 
 struct SngGraph {
@@ -141,6 +182,12 @@ inline int hip_fail(SngEnv *env, hipError_t e, const char *what) {
     return fail(env, SNG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// a handle's buffers could not be made: "<what> buffers" where the memory ran out, else HIP's own text
+inline int create_fail(SngEnv *env, hipError_t e, const std::string &what) {
+    return e == hipErrorOutOfMemory ? fail(env, SNG_ERR_OUT_OF_MEMORY, what + " buffers")
+                                    : hip_fail(env, e, (what + " create").c_str());
+}
+
 #define HIP_TRY(env, expr)                                   \
     do {                                                     \
         hipError_t _e = (expr);                              \
@@ -157,8 +204,6 @@ inline int hip_fail(SngEnv *env, hipError_t e, const char *what) {
 #define ON_DEVICE_OF(env)               \
     DeviceScope dev_((env)->device);    \
     HIP_TRY(env, dev_.err)
-
-inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
 
 // --- the loaded day (DayKey, t, day_finished, gen_mode, gen_loaded) ---
 inline void load_day(SngEnv *env, const DayKey &k) { env->p = with_day(env->p, k); }
@@ -205,6 +250,26 @@ inline InfoPtrs info_ptrs(const SngInfo *i) {
     o.vehicle_soc = i->vehicle_soc;
     o.flag_any = i->flag_summary;
     return o;
+}
+
+// --- what depends on a policy's form ---
+inline int policy_weights_ok(const SngPolicy *pol, const SngMlpWeights *w, std::string *why) {
+    return pol->net ? net_weights_check(pol->net_spec, w, why) : policy_weights_check(pol->spec, w, why);
+}
+inline void policy_pack_image(const SngPolicy *pol, const SngMlpWeights &w, float *img) {
+    if (pol->net) net_pack(pol->net_image, pol->net_spec, w, img);
+    else policy_pack(pol->image, pol->spec, w, img);
+}
+// One actor launch over the env's rows, by the policy's own kernel.
+inline hipError_t launch_actor(const SngPolicy *pol, const float *obs, const float *noise, float *actions,
+                               float *env_actions, int64_t E, hipStream_t stream) {
+    return pol->net ? launch_policy_net(pol->img.d, pol->net_image, obs, noise, actions, env_actions, E, stream)
+                    : launch_policy(pol->img.d, pol->image, obs, noise, actions, env_actions, E, stream);
+}
+// The form of a policy's captured day: sng_step_plan.h decides it, per kind of policy.
+inline bool policy_graph_fused(const SngPolicy *pol, const Params &p, const InfoPtrs &ip, bool traj, bool step_nodes,
+                               bool force) {
+    return (pol->net ? policy_net_day_fused(p, ip, traj, step_nodes, force) : policy_day_fused(p, ip, traj, step_nodes, force)) != 0;
 }
 
 inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }

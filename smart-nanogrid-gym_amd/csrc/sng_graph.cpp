@@ -6,20 +6,6 @@
 
 using namespace sng;
 
-// The form of a policy's captured day: sng_step_plan.h decides it, per kind of policy (sng_policy_create's 64-64
-// actor, sng_policy_create_net's actor of any width).
-static bool policy_graph_fused(const SngPolicy *policy, const Params &p, const InfoPtrs &ip, bool traj, bool step_nodes,
-                               bool force) {
-    if (policy->net) return policy_net_day_fused(p, ip, traj, step_nodes, force) != 0;
-    return policy_day_fused(p, ip, traj, step_nodes, force) != 0;
-}
-// One actor launch over the env's rows, by the policy's own kernel.
-static hipError_t launch_actor(const SngPolicy *policy, const float *obs, const float *noise, float *actions,
-                               float *env_actions, int64_t E, hipStream_t stream) {
-    if (policy->net) return launch_policy_net(policy->d_img, policy->net_image, obs, noise, actions, env_actions, E, stream);
-    return launch_policy(policy->d_img, policy->image, obs, noise, actions, env_actions, E, stream);
-}
-
 // sng_graph_create and sng_graph_create_policy.  Without a policy, `actions` holds the day's T action blocks.  With
 // one (sng_policy.cpp), every step's actions are the actor's answer to the observation before it: `noise` (T
 // blocks, may be null) takes the place of the actions stream, `actions_out` receives a, and the step nodes read the
@@ -116,7 +102,7 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
     // a source's fill of every day's block and its counter's bump: the chain's first nodes
     const size_t noise_day = noise_source ? (size_t)p.T * (size_t)E * (size_t)A : 0;
     if (noise_source && e == hipSuccess)
-        e = launch_noise_fill(noise_source->spec, noise_source->d_params, noise_source->d_counter, p.env_offset,
+        e = launch_noise_fill(noise_source->spec, noise_source->params.d, noise_source->d_counter, p.env_offset,
                               const_cast<float *>(noise), days, p.T, E, cs);
     if (g->overlapped && e == hipSuccess) {   // fork
         e = hipEventRecord(stepped[0], cs);
@@ -146,7 +132,7 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
             float *a_d = actions_out + (traj ? (size_t)d * (size_t)p.T * act_block : 0);
             const float *noise_d = noise ? noise + (size_t)d * noise_day : nullptr;
             if (e == hipSuccess && g->day_kernel)
-                e = launch_policy_day(pd, ds, ipd, policy->d_img, policy->image, noise_d, obs0, obs_d, a_d, reward_d, done_d,
+                e = launch_policy_day(pd, ds, ipd, policy->img.d, policy->image, noise_d, obs0, obs_d, a_d, reward_d, done_d,
                                       E, (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step,
                                       traj ? (int64_t)act_block : 0);
             for (int t = 0; e == hipSuccess && !g->day_kernel && t < p.T; ++t) {

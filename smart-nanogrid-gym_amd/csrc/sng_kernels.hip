@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "sng.h"
 #include "sng_launch.h"
 #include "sng_layout.h"
@@ -450,11 +452,10 @@ hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPt
         case 16: l = policy_day_launch<16>(pl, E, kern); break;
     }
     if (!kern) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
-    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
     // every step's block 16 B aligned, or none is promised to be
     const int64_t noise_step = noise ? E * (int64_t)p.act_dim : 0;
-    if (obs_step % 4 != 0 || !a16(obs0) || !a16(noise) || noise_step % 4 != 0) vec_io = 0;
-    const int vec_act = (a16(actions_out) && act_step % 4 == 0) ? 1 : 0;
+    if (obs_step % 4 != 0 || !aligned16(obs0) || !aligned16(noise) || noise_step % 4 != 0) vec_io = 0;
+    const int vec_act = (aligned16(actions_out) && act_step % 4 == 0) ? 1 : 0;
     // without noise the prefetch reads step 0's block of a, which is never used
     return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, img, m, noise ? noise : actions_out,
                          noise_step, noise ? 1 : 0, obs0, obs, actions_out, reward, done, E, 0, p.T, vec_io, vec_act,
@@ -463,19 +464,21 @@ hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPt
 
 // One workgroup's tiles are more than 64 KB of dynamic LDS from 46 chargers on (150,528 B at 128): allowed once
 // per kernel, up to the CU's 160 KB, and asked for when the first policy is created -- outside any stream capture.
+// raise_lds_limit asks for every kernel of its list and returns the first refusal; the *_kernels_init functions
+// keep its answer.
+template <class... Kernels>
+static hipError_t raise_lds_limit(int bytes, Kernels... kernels) {
+    hipError_t first = hipSuccess;
+    for (const void *k : {reinterpret_cast<const void *>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
 constexpr int kPolicyMaxLds = 160 * 1024;
 hipError_t policy_kernels_init() {
-    static const hipError_t set = [] {
-        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_kernel<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
-        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
-        const hipError_t c = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_net_kernel<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
-        const hipError_t d = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_net_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPolicyMaxLds);
-        return a != hipSuccess ? a : b != hipSuccess ? b : c != hipSuccess ? c : d;
-    }();
+    static const hipError_t set = raise_lds_limit(kPolicyMaxLds, policy_kernel<false>, policy_kernel<true>,
+                                                  policy_net_kernel<false>, policy_net_kernel<true>);
     return set;
 }
 
@@ -485,8 +488,7 @@ static hipError_t launch_policy_kernel(const float *img, const PolicyImage &m, c
     const size_t lds = policy_lds_bytes(m.O, m.A);
     if (lds > (size_t)kPolicyMaxLds) return hipErrorInvalidValue;
     if (lds > 64u * 1024u && policy_kernels_init() != hipSuccess) return policy_kernels_init();
-    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
-    const int vec = (a16(obs) && a16(noise) && a16(actions) && a16(env_actions)) ? 1 : 0;
+    const int vec = (aligned16(obs) && aligned16(noise) && aligned16(actions) && aligned16(env_actions)) ? 1 : 0;
     return launch_kernel(policy_kernel<TANH>, blocks_for(E, kWave), dim3(kPolicyBlock), lds, stream, nullptr, nullptr, img, m,
                          obs, noise, actions, env_actions, E, vec);
 }
@@ -516,13 +518,7 @@ hipError_t launch_policy_net(const float *img, const NetImage &m, const float *o
 // rollout_gae_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises the policy kernels': two observation
 // tiles, the hidden rows and the noise tile are more than 64 KB from 35 chargers on.
 hipError_t ppo_kernels_init() {
-    static const hipError_t set = [] {
-        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_gae_kernel<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMaxLds);
-        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_gae_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMaxLds);
-        return a != hipSuccess ? a : b;
-    }();
+    static const hipError_t set = raise_lds_limit(kPpoMaxLds, rollout_gae_kernel<false>, rollout_gae_kernel<true>);
     return set;
 }
 
@@ -531,14 +527,13 @@ hipError_t ppo_kernels_init() {
 hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoRollout &r, int64_t E, int T,
                               hipStream_t stream) {
     const float *noise = r.logp ? r.noise : nullptr;   // no log-probability stage without both
-    const bool two = ppo_lds_bytes(m.v.O, m.A, true, noise != nullptr) <= (size_t)kPpoMaxLds;
-    const size_t lds = ppo_lds_bytes(m.v.O, m.A, two, noise != nullptr);
+    const bool two = ppo_lds_bytes(m.v.O, m.head.A, true, noise != nullptr) <= (size_t)kPpoMaxLds;
+    const size_t lds = ppo_lds_bytes(m.v.O, m.head.A, two, noise != nullptr);
     if (lds > (size_t)kPpoMaxLds || T < 1 || E < 1 || r.days < 1 || r.days > kPpoMaxLaunchDays) return hipErrorInvalidValue;
     if (lds > 64u * 1024u && ppo_kernels_init() != hipSuccess) return ppo_kernels_init();
-    const auto a16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
     // every step's block 16 B aligned, or none is promised to be
-    const int vec_obs = (a16(r.obs) && (E * (int64_t)m.v.O) % 4 == 0) ? 1 : 0;
-    const int vec_noise = (a16(noise) && (E * (int64_t)m.A) % 4 == 0) ? 1 : 0;
+    const int vec_obs = (aligned16(r.obs) && (E * (int64_t)m.v.O) % 4 == 0) ? 1 : 0;
+    const int vec_noise = (aligned16(noise) && (E * (int64_t)m.head.A) % 4 == 0) ? 1 : 0;
     const dim3 grid((unsigned)((E + kWave - 1) / kWave), (unsigned)r.days), block(kPolicyBlock);
     const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
     return m.v.activation == POLICY_RELU
@@ -553,13 +548,7 @@ hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoR
 // value_net_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises policy_net_kernel's: the same tiles,
 // above 64 KB from a hidden1 of 224 on.
 hipError_t ppo_net_kernels_init() {
-    static const hipError_t set = [] {
-        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(value_net_kernel<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetMaxLds);
-        const hipError_t b = hipFuncSetAttribute(reinterpret_cast<const void *>(value_net_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetMaxLds);
-        return a != hipSuccess ? a : b;
-    }();
+    static const hipError_t set = raise_lds_limit((int)kNetMaxLds, value_net_kernel<false>, value_net_kernel<true>);
     return set;
 }
 
@@ -586,12 +575,13 @@ hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRo
     const dim3 sgrid((unsigned)((E + kScanBlock - 1) / kScanBlock), (unsigned)scan_rows), sblock(kScanBlock);
     const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
     const float *values = r.values;
-    return noise ? launch_kernel(gae_scan_kernel<true>, sgrid, sblock, gae_scan_lds_bytes(m.head.A), stream, nullptr,
-                                 nullptr, img, m.head.log_std, m.head.inv_std, (int)m.head.A, r.reward, r.done, noise,
-                                 values, r.advantages, r.returns, r.logp, E, T, (int)r.days, g, gl)
-                 : launch_kernel(gae_scan_kernel<false>, sgrid, sblock, 0, stream, nullptr, nullptr, img,
-                                 m.head.log_std, m.head.inv_std, (int)m.head.A, r.reward, r.done, noise, values,
-                                 r.advantages, r.returns, r.logp, E, T, (int)r.days, g, gl);
+    const GaussHead &h = m.head;
+    return noise ? launch_kernel(gae_scan_kernel<true>, sgrid, sblock, gae_scan_lds_bytes(h.A), stream, nullptr, nullptr, img,
+                                 h.log_std, h.inv_std, (int)h.A, r.reward, r.done, noise, values, r.advantages,
+                                 r.returns, r.logp, E, T, (int)r.days, g, gl)
+                 : launch_kernel(gae_scan_kernel<false>, sgrid, sblock, 0, stream, nullptr, nullptr, img, h.log_std,
+                                 h.inv_std, (int)h.A, r.reward, r.done, noise, values, r.advantages, r.returns, r.logp,
+                                 E, T, (int)r.days, g, gl);
 }
 
 // A source's fill and, behind it, its counter's bump: grid x over the row's groups of four elements, y over the blocks.
@@ -603,7 +593,7 @@ hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint
     const int64_t blocks = (row + per - 1) / per;
     if (blocks > 2147483647ll) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks, (unsigned)(days < kNoiseMaxGridDays ? days : kNoiseMaxGridDays)), block(kNoiseBlock);
-    const int vec = (((uintptr_t)out & 15u) == 0 && row % 4 == 0) ? 1 : 0;
+    const int vec = (aligned16(out) && row % 4 == 0) ? 1 : 0;
     const float theta = (float)spec.theta, dt = (float)spec.dt;
     const hipError_t e =
         spec.kind == SNG_NOISE_OU

@@ -13,6 +13,9 @@
 
 namespace sng {
 
+// a pointer a kernel may read or write 16 bytes a lane through
+inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+
 // ev_start / ev_stop (both or neither): stamped with the dispatch's own begin / end, the kernel's device time
 hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,

@@ -1,6 +1,7 @@
 // sng_noise.cpp -- the action-noise source's handle (sng_noise_create / set_params / fill / get_counter / set_counter /
 // destroy) and the host-only sng_noise_host_fill.  The arithmetic is sng_noise_host.h's on both sides; the kernel is
 // sng_noise.h's.  The graphs that begin with a fill are captured in sng_graph.cpp.
+#include <algorithm>
 #include <vector>
 
 #include "sng_env.h"
@@ -17,16 +18,14 @@ int sng_noise_create(SngEnv *env, const SngNoiseSpec *spec, SngNoise **out) {
     SngNoise *nz = new SngNoise();
     nz->env = env;
     nz->spec = *spec;
-    const size_t bytes = 2 * (size_t)spec->act_dim * sizeof(float);
-    hipError_t e = hipMalloc((void **)&nz->d_params, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&nz->h_params, bytes, hipHostMallocDefault);
+    const size_t floats = 2 * (size_t)spec->act_dim;
+    hipError_t e = nz->params.create(floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&nz->d_counter, sizeof(uint64_t));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nz->uploaded, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemset(nz->d_params, 0, bytes);
+    if (e == hipSuccess) e = nz->params.upload_now([&](float *h) { std::fill(h, h + floats, 0.f); });
     if (e == hipSuccess) e = hipMemset(nz->d_counter, 0, sizeof(uint64_t));
     if (e != hipSuccess) {
         sng_noise_destroy(nz);
-        return e == hipErrorOutOfMemory ? fail(env, SNG_ERR_OUT_OF_MEMORY, "noise buffers") : hip_fail(env, e, "noise create");
+        return create_fail(env, e, "noise");
     }
     *out = nz;
     return SNG_OK;
@@ -38,11 +37,7 @@ int sng_noise_set_params(SngNoise *nz, const float *mu, const float *scale, void
     std::string why;
     if (int rc = noise_params_check(nz->spec.act_dim, mu, scale, &why)) return fail(env, rc, why);
     ON_DEVICE_OF(env);
-    HIP_TRY(env, hipEventSynchronize(nz->uploaded));   // the upload before this one has read the mirror
-    noise_pack_params(nz->spec, mu, scale, nz->h_params);
-    HIP_TRY(env, hipMemcpyAsync(nz->d_params, nz->h_params, 2 * (size_t)nz->spec.act_dim * sizeof(float),
-                                hipMemcpyHostToDevice, as_stream(stream)));
-    HIP_TRY(env, hipEventRecord(nz->uploaded, as_stream(stream)));
+    HIP_TRY(env, nz->params.upload(as_stream(stream), [&](float *h) { noise_pack_params(nz->spec, mu, scale, h); }));
     return SNG_OK;
 }
 
@@ -52,7 +47,7 @@ int sng_noise_fill(SngNoise *nz, float *out, int32_t days, void *stream) {
     if (days < 1) return fail(env, SNG_ERR_INVALID_ARGUMENT, "noise fill: days = " + std::to_string(days) + " must be >= 1");
     if (!out) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null noise output");
     ON_DEVICE_OF(env);
-    HIP_TRY(env, launch_noise_fill(nz->spec, nz->d_params, nz->d_counter, env->p.env_offset, out, days, env->p.T, env->E,
+    HIP_TRY(env, launch_noise_fill(nz->spec, nz->params.d, nz->d_counter, env->p.env_offset, out, days, env->p.T, env->E,
                                    as_stream(stream)));
     return SNG_OK;
 }
@@ -79,13 +74,8 @@ int sng_noise_set_counter(SngNoise *nz, uint64_t counter, void *stream) {
 void sng_noise_destroy(SngNoise *nz) {
     if (!nz) return;
     DeviceScope scope(nz->env->device);
-    if (nz->uploaded) {
-        (void)hipEventSynchronize(nz->uploaded);
-        (void)hipEventDestroy(nz->uploaded);
-    }
-    if (nz->d_params) (void)hipFree(nz->d_params);
+    nz->params.destroy();
     if (nz->d_counter) (void)hipFree(nz->d_counter);
-    if (nz->h_params) (void)hipHostFree(nz->h_params);
     delete nz;
 }
 

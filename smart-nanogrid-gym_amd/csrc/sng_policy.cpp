@@ -1,7 +1,7 @@
 // sng_policy.cpp -- the MLP actor's handle (sng_policy_create / sng_policy_create_net / set_weights / actions /
 // destroy) and the host-only sng_policy_host_actions and sng_policy_net_host_actions.  The 64-64 actor's arithmetic
 // is sng_policy_host.h's on the host and sng_policy.h's on the device, the any-width actor's sng_policy_net_host.h's
-// and sng_policy_net.h's; one handle type serves both (SngPolicy::net says which).  The graphs with the actor in the
+// and sng_policy_net.h's; one handle type serves both (sng_env.h, SngPolicy, and what depends on its form).  The graphs with the actor in the
 // loop are captured in sng_graph.cpp.
 #include <algorithm>
 #include <cstring>
@@ -10,28 +10,33 @@
 
 using namespace sng;
 
-// The device image, its pinned mirror, the clipped-actions block and the upload event of a new policy, with zero
-// weights (and the spec's bounds) in the image until the first upload.  Destroys `pol` where it fails.
-static int policy_buffers(SngEnv *env, SngPolicy *pol) {
-    const int O = pol->net ? pol->net_spec.obs_dim : pol->spec.obs_dim, A = pol->net ? pol->net_spec.act_dim : pol->spec.act_dim;
-    const int H1 = pol->net ? pol->net_spec.hidden1 : kPolicyHidden, H2 = pol->net ? pol->net_spec.hidden2 : kPolicyHidden;
-    const size_t bytes = (pol->net ? pol->net_image.floats : pol->image.floats) * sizeof(float);
+// What the two creates share, `pol` holding its form's spec and image: the dims and the owned copy of the bounds
+// (*low_at / *high_at: the spec's pointers to them), the device image with zero weights (and the bounds) in it until the
+// first upload, and the clipped-actions block.  Destroys `pol` where it fails.
+static int policy_finish_create(SngEnv *env, SngPolicy *pol, int O, int A, int H1, int H2, size_t floats,
+                                const float **low_at, const float **high_at, SngPolicy **out) {
+    pol->env = env;
+    pol->O = O, pol->A = A, pol->H1 = H1, pol->H2 = H2;
+    pol->floats = floats;
+    if (*low_at) {
+        pol->clip_low.assign(*low_at, *low_at + A);
+        pol->clip_high.assign(*high_at, *high_at + A);
+        *low_at = pol->clip_low.data();
+        *high_at = pol->clip_high.data();
+    }
     (void)policy_kernels_init();   // a refusal surfaces at the launch that needs the room
-    hipError_t e = hipMalloc((void **)&pol->d_img, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&pol->h_img, bytes, hipHostMallocDefault);
+    hipError_t e = pol->img.create(floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&pol->d_env_actions, (size_t)env->E * (size_t)A * sizeof(float));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&pol->uploaded, hipEventDisableTiming);
     if (e == hipSuccess) {
         const std::vector<float> zero(std::max({(size_t)H1 * (size_t)O, (size_t)H2 * (size_t)H1, (size_t)A * (size_t)H2}));
         const SngMlpWeights w{zero.data(), zero.data(), zero.data(), zero.data(), zero.data(), zero.data()};
-        if (pol->net) net_pack(pol->net_image, pol->net_spec, w, pol->h_img);
-        else policy_pack(pol->image, pol->spec, w, pol->h_img);
-        e = hipMemcpy(pol->d_img, pol->h_img, bytes, hipMemcpyHostToDevice);
+        e = pol->img.upload_now([&](float *img) { policy_pack_image(pol, w, img); });
     }
     if (e != hipSuccess) {
         sng_policy_destroy(pol);
-        return e == hipErrorOutOfMemory ? fail(env, SNG_ERR_OUT_OF_MEMORY, "policy buffers") : hip_fail(env, e, "policy create");
+        return create_fail(env, e, "policy");
     }
+    *out = pol;
     return SNG_OK;
 }
 
@@ -43,18 +48,10 @@ int sng_policy_create(SngEnv *env, const SngMlpSpec *spec, SngPolicy **out) {
     if (int rc = policy_spec_check(spec, env->p.obs_dim, env->p.act_dim, &why)) return fail(env, rc, why);
     ON_DEVICE_OF(env);
     SngPolicy *pol = new SngPolicy();
-    pol->env = env;
     pol->spec = *spec;
-    if (spec->clip_low) {
-        pol->clip_low.assign(spec->clip_low, spec->clip_low + spec->act_dim);
-        pol->clip_high.assign(spec->clip_high, spec->clip_high + spec->act_dim);
-        pol->spec.clip_low = pol->clip_low.data();
-        pol->spec.clip_high = pol->clip_high.data();
-    }
     pol->image = policy_image(spec->obs_dim, spec->act_dim, spec->activation, spec->clip_low != nullptr);
-    if (int rc = policy_buffers(env, pol)) return rc;
-    *out = pol;
-    return SNG_OK;
+    return policy_finish_create(env, pol, spec->obs_dim, spec->act_dim, kPolicyHidden, kPolicyHidden, pol->image.floats,
+                                &pol->spec.clip_low, &pol->spec.clip_high, out);
 }
 
 int sng_policy_create_net(SngEnv *env, const SngMlpNetSpec *spec, SngPolicy **out) {
@@ -63,36 +60,21 @@ int sng_policy_create_net(SngEnv *env, const SngMlpNetSpec *spec, SngPolicy **ou
     if (int rc = net_spec_check(spec, env->p.obs_dim, env->p.act_dim, &why)) return fail(env, rc, why);
     ON_DEVICE_OF(env);
     SngPolicy *pol = new SngPolicy();
-    pol->env = env;
     pol->net = true;
     pol->net_spec = *spec;
-    if (spec->low) {
-        pol->clip_low.assign(spec->low, spec->low + spec->act_dim);
-        pol->clip_high.assign(spec->high, spec->high + spec->act_dim);
-        pol->net_spec.low = pol->clip_low.data();
-        pol->net_spec.high = pol->clip_high.data();
-    }
     pol->net_image = net_image(spec->obs_dim, spec->act_dim, spec->hidden1, spec->hidden2, spec->activation, spec->output,
                                spec->low != nullptr);
-    if (int rc = policy_buffers(env, pol)) return rc;
-    *out = pol;
-    return SNG_OK;
+    return policy_finish_create(env, pol, spec->obs_dim, spec->act_dim, spec->hidden1, spec->hidden2, pol->net_image.floats,
+                                &pol->net_spec.low, &pol->net_spec.high, out);
 }
 
 int sng_policy_set_weights(SngPolicy *pol, const SngMlpWeights *w, void *stream) {
     if (!pol) return SNG_ERR_INVALID_ARGUMENT;
     SngEnv *env = pol->env;
     std::string why;
-    if (int rc = pol->net ? net_weights_check(pol->net_spec, w, &why) : policy_weights_check(pol->spec, w, &why))
-        return fail(env, rc, why);
+    if (int rc = policy_weights_ok(pol, w, &why)) return fail(env, rc, why);
     ON_DEVICE_OF(env);
-    HIP_TRY(env, hipEventSynchronize(pol->uploaded));   // the upload before this one has read the mirror
-    if (pol->net) net_pack(pol->net_image, pol->net_spec, *w, pol->h_img);
-    else policy_pack(pol->image, pol->spec, *w, pol->h_img);
-    const size_t floats = pol->net ? pol->net_image.floats : pol->image.floats;
-    HIP_TRY(env, hipMemcpyAsync(pol->d_img, pol->h_img, floats * sizeof(float), hipMemcpyHostToDevice,
-                                as_stream(stream)));
-    HIP_TRY(env, hipEventRecord(pol->uploaded, as_stream(stream)));
+    HIP_TRY(env, pol->img.upload(as_stream(stream), [&](float *img) { policy_pack_image(pol, *w, img); }));
     return SNG_OK;
 }
 
@@ -102,23 +84,15 @@ int sng_policy_actions(SngPolicy *pol, const float *obs, const float *noise, flo
     SngEnv *env = pol->env;
     if (!obs || !actions) return fail(env, SNG_ERR_INVALID_ARGUMENT, "null argument");
     ON_DEVICE_OF(env);
-    if (pol->net)
-        HIP_TRY(env, launch_policy_net(pol->d_img, pol->net_image, obs, noise, actions, env_actions, env->E, as_stream(stream)));
-    else
-        HIP_TRY(env, launch_policy(pol->d_img, pol->image, obs, noise, actions, env_actions, env->E, as_stream(stream)));
+    HIP_TRY(env, launch_actor(pol, obs, noise, actions, env_actions, env->E, as_stream(stream)));
     return SNG_OK;
 }
 
 void sng_policy_destroy(SngPolicy *pol) {
     if (!pol) return;
     DeviceScope scope(pol->env->device);
-    if (pol->uploaded) {
-        (void)hipEventSynchronize(pol->uploaded);
-        (void)hipEventDestroy(pol->uploaded);
-    }
-    if (pol->d_img) (void)hipFree(pol->d_img);
+    pol->img.destroy();
     if (pol->d_env_actions) (void)hipFree(pol->d_env_actions);
-    if (pol->h_img) (void)hipHostFree(pol->h_img);
     delete pol;
 }
 

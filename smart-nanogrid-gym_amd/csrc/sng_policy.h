@@ -51,6 +51,30 @@ __device__ __forceinline__ void policy_chains(float (&acc)[NJ], const float *__r
     }
 }
 
+// The output stage of a lane's row: outputs [c0, c0 + NJ) of the output layer (acc) to s_a [64][A] (a = mean, + the
+// noise s_a holds on entry when `noise`) and s_env [64][A] (a clipped to the image's bounds lo, hi where it has them);
+// the padded outputs past A are dropped.
+template <int NJ>
+__device__ __forceinline__ void policy_output_store(const PolicyImage &m, const float (&acc)[NJ], int c0,
+                                                    float *__restrict__ s_a, float *__restrict__ s_env, bool noise,
+                                                    int lane, const float *lo, const float *hi) {
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int j = c0 + jj;
+        if (j < m.A) {
+            const int at = lane * m.A + j;
+            const float a = noise ? acc[jj] + s_a[at] : acc[jj];
+            s_a[at] = a;
+            float c = a;
+            if (m.clip) {
+                c = a < lo[j] ? lo[j] : a;
+                c = hi[j] < c ? hi[j] : c;
+            }
+            s_env[at] = c;
+        }
+    }
+}
+
 // policy_kernel's form of the tile.  One workgroup of kPolicyWaves wavefronts: s_obs [64][O] -> s_a [64][A] (a = mean, + the noise s_a holds on entry
 // when `noise`) and s_env [64][A] (what the env is stepped with: a clipped to the image's bounds where it has them).
 // s_h: the rows' hidden values, [64][kPolicyHStride].  Lane l of every wavefront works on row l; wavefront `wave`
@@ -82,21 +106,7 @@ __device__ __forceinline__ void mlp_actor_block(const float *__restrict__ img, c
     const float *lo = img + m.low, *hi = img + m.high;
     for (int c0 = wave * NJ; c0 < m.AP; c0 += kPolicyWaves * NJ) {
         policy_chains<NJ>(acc, hrow, H, img + m.w3t, m.AP, img + m.b3, c0);
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int j = c0 + jj;
-            if (j < m.A) {
-                const int at = lane * m.A + j;
-                const float a = noise ? acc[jj] + s_a[at] : acc[jj];
-                s_a[at] = a;
-                float c = a;
-                if (m.clip) {
-                    c = a < lo[j] ? lo[j] : a;
-                    c = hi[j] < c ? hi[j] : c;
-                }
-                s_env[at] = c;
-            }
-        }
+        policy_output_store<NJ>(m, acc, c0, s_a, s_env, noise, lane, lo, hi);
     }
 }
 
@@ -169,21 +179,7 @@ __device__ __forceinline__ void mlp_actor_tile(const float *__restrict__ img, co
     for (int c0 = 0; c0 < m.AP; c0 += NJ) {
         float o[NJ];
         policy_chains<NJ, kWave>(o, hcol, H, img + m.w3t, m.AP, img + m.b3, c0);
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int j = c0 + jj;
-            if (j < m.A) {
-                const int at = lane * m.A + j;
-                const float a = noise ? o[jj] + s_a[at] : o[jj];
-                s_a[at] = a;
-                float c = a;
-                if (m.clip) {
-                    c = a < lo[j] ? lo[j] : a;
-                    c = hi[j] < c ? hi[j] : c;
-                }
-                s_env[at] = c;
-            }
-        }
+        policy_output_store<NJ>(m, o, c0, s_a, s_env, noise, lane, lo, hi);
     }
 }
 

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "sng.h"
 
@@ -83,23 +84,26 @@ inline int policy_spec_check(const SngMlpSpec *s, int obs_dim, int act_dim, std:
     return SNG_OK;
 }
 
-// Non-finite weights are refused at upload.
-inline int policy_weights_check(const SngMlpSpec &s, const SngMlpWeights *w, std::string *why) {
-    auto no = [&](const char *msg) {
+// Non-finite weights are refused at upload: the six arrays of a net of O inputs, hidden widths H1 and H2 and A outputs.
+// `what` names them in the message: "policy", or "value net" for a PPO head's (sng_ppo_host.h).
+inline int mlp_weights_check(int O, int H1, int H2, int A, const char *what, const SngMlpWeights *w, std::string *why) {
+    auto no = [&](const std::string &msg) {
         if (why) *why = msg;
         return (int)SNG_ERR_INVALID_ARGUMENT;
     };
-    if (!w || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3) return no("null policy weights");
-    constexpr size_t H = kPolicyHidden;
+    if (!w || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3) return no(std::string("null ") + what + " weights");
+    const size_t n1 = (size_t)H1, n2 = (size_t)H2, n3 = (size_t)A;
     const struct {
         const float *v;
         size_t n;
-    } parts[] = {{w->w1, H * (size_t)s.obs_dim}, {w->b1, H}, {w->w2, H * H}, {w->b2, H},
-                 {w->w3, (size_t)s.act_dim * H}, {w->b3, (size_t)s.act_dim}};
+    } parts[] = {{w->w1, n1 * (size_t)O}, {w->b1, n1}, {w->w2, n2 * n1}, {w->b2, n2}, {w->w3, n3 * n2}, {w->b3, n3}};
     for (const auto &part : parts)
         for (size_t i = 0; i < part.n; ++i)
-            if (!std::isfinite(part.v[i])) return no("non-finite policy weight");
+            if (!std::isfinite(part.v[i])) return no(std::string("non-finite ") + what + " weight");
     return SNG_OK;
+}
+inline int policy_weights_check(const SngMlpSpec &s, const SngMlpWeights *w, std::string *why) {
+    return mlp_weights_check(s.obs_dim, kPolicyHidden, kPolicyHidden, s.act_dim, "policy", w, why);
 }
 
 // The weights and the spec's clip bounds into `img` (PolicyImage::floats floats).
@@ -135,33 +139,48 @@ inline float policy_clip(float a, float low, float high) {
     return high < c ? high : c;
 }
 
+// The contract's three layers over `rows` observation rows [rows][O], on a packed image: every output is the chain
+// from its bias over the layer's k = 0 .. K-1 in order, one fmaf and so one rounding a term.  bias[l]: where layer
+// l's biases begin in img; at(l, j, k): where its W[j][k] is (the two images differ in nothing else).  Row r's output
+// layer goes to out(r, j, mean).
+template <class WeightAt, class Output>
+inline void mlp_forward_host(int O, int H1, int H2, int A, int activation, const float *img, const size_t (&bias)[3],
+                             WeightAt at, int64_t rows, const float *obs, Output out) {
+    std::vector<float> h1((size_t)H1), h2((size_t)H2);
+    for (int64_t r = 0; r < rows; ++r) {
+        const float *x = obs + (size_t)r * (size_t)O;
+        for (int j = 0; j < H1; ++j) {
+            float h = img[bias[0] + j];
+            for (int k = 0; k < O; ++k) h = std::fmaf(x[k], img[at(0, j, k)], h);
+            h1[j] = policy_activate(activation, h);
+        }
+        for (int j = 0; j < H2; ++j) {
+            float h = img[bias[1] + j];
+            for (int k = 0; k < H1; ++k) h = std::fmaf(h1[k], img[at(1, j, k)], h);
+            h2[j] = policy_activate(activation, h);
+        }
+        for (int j = 0; j < A; ++j) {
+            float h = img[bias[2] + j];
+            for (int k = 0; k < H2; ++k) h = std::fmaf(h2[k], img[at(2, j, k)], h);
+            out(r, j, h);
+        }
+    }
+}
+
 // The contract, on the packed image: `rows` observation rows [rows][O] -> actions [rows][A] (a) and, where
 // env_actions is given, the actions the env is stepped with.  noise [rows][A] may be null.
 inline void mlp_actor_host(const PolicyImage &m, const float *img, int64_t rows, const float *obs, const float *noise,
                            float *actions, float *env_actions) {
     constexpr int H = kPolicyHidden;
-    float h1[H], h2[H];
-    for (int64_t r = 0; r < rows; ++r) {
-        const float *x = obs + (size_t)r * (size_t)m.O;
-        for (int j = 0; j < H; ++j) {
-            float h = img[m.b1 + j];
-            for (int k = 0; k < m.O; ++k) h = std::fmaf(x[k], img[m.w1t + (size_t)k * H + j], h);
-            h1[j] = policy_activate(m.activation, h);
-        }
-        for (int j = 0; j < H; ++j) {
-            float h = img[m.b2 + j];
-            for (int k = 0; k < H; ++k) h = std::fmaf(h1[k], img[m.w2t + (size_t)k * H + j], h);
-            h2[j] = policy_activate(m.activation, h);
-        }
-        for (int j = 0; j < m.A; ++j) {
-            float h = img[m.b3 + j];
-            for (int k = 0; k < H; ++k) h = std::fmaf(h2[k], img[m.w3t + (size_t)k * m.AP + j], h);
+    const size_t w[3] = {m.w1t, m.w2t, m.w3t}, ld[3] = {(size_t)H, (size_t)H, (size_t)m.AP};   // [in][out]
+    mlp_forward_host(
+        m.O, H, H, m.A, m.activation, img, {m.b1, m.b2, m.b3}, [&](int l, int j, int k) { return w[l] + (size_t)k * ld[l] + j; },
+        rows, obs, [&](int64_t r, int j, float mean) {
             const size_t at = (size_t)r * (size_t)m.A + (size_t)j;
-            const float a = noise ? h + noise[at] : h;
+            const float a = noise ? mean + noise[at] : mean;
             actions[at] = a;
             if (env_actions) env_actions[at] = m.clip ? policy_clip(a, img[m.low + j], img[m.high + j]) : a;
-        }
-    }
+        });
 }
 
 }  // namespace sng

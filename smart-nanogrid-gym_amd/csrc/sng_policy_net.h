@@ -1,5 +1,6 @@
 // sng_policy_net.h -- the MLP actor of any width on the f32-input MFMA: policy_net_kernel, the device side of
-// sng_policy_create_net.  Included by sng_kernels.hip only, behind sng_policy.h.
+// sng_policy_create_net, and net_trunk, everything of it up to the output stage, which value_net_kernel
+// (sng_ppo_net.h) runs a value net through as well.  Included by sng_kernels.hip only, behind sng_policy.h.
 //
 // The arithmetic is the contract of sng_policy_net_host.h: every output is the k-ordered f32 fmaf chain started from
 // the bias.  v_mfma_f32_32x32x2_f32 computes D = fma(a_k1, b_k1, fma(a_k0, b_k0, C)) for 32 rows x 32 outputs, one
@@ -103,13 +104,25 @@ __device__ __forceinline__ void net_store_hidden(float *__restrict__ out, int st
     for (int r = 0; r < 16; ++r) out[net_acc_row(r, lane) * stride + (lane & 31)] = policy_activation<TANH>(acc[r]);
 }
 
-// The actor over E rows.  obs [E][O], noise [E][A] or null, actions [E][A] (a), env_actions [E][A] or null.
-template <bool TANH>
-__global__ __launch_bounds__(kNetBlock) void policy_net_kernel(const float *__restrict__ img, NetImage m,
-                                                               const float *__restrict__ obs,
-                                                               const float *__restrict__ noise,
-                                                               float *__restrict__ actions,
-                                                               float *__restrict__ env_actions, int64_t E) {
+// What net_trunk hands a kernel's output stage: the output tile's accumulators (real where has_out), and where the
+// wavefront stands: the workgroup's first row e0 and its `rows` rows with an env, the first row row0 of the
+// wavefront's row tile (rt * kNetTile) and its output tile otile.
+struct NetTrunk {
+    net_f32x16 out;
+    int64_t e0;
+    int rows, row0, otile;
+    bool has_out;
+};
+
+// The trunk of policy_net_kernel and value_net_kernel (sng_ppo_net.h): a workgroup's 64 rows of obs [E][O] staged,
+// both hidden layers, and the output tile's chains advanced over every chunk of hidden2.  ONE_TILE: the output layer
+// has one tile (the value net's), known at compile time.  That flag, the image's description by value, the row tile
+// as its first row and the lane left to the kernels are what make both kernels compile to the code they had with the
+// trunk written out in each, but for the sense of a branch behind the layers; other spellings of this interface cost
+// either kernel about half a percent (profiles/mlp_refactor_ab.txt).
+template <bool TANH, bool ONE_TILE = false>
+__device__ __forceinline__ NetTrunk net_trunk(const float *__restrict__ img, const NetImage m,
+                                              const float *__restrict__ obs, int64_t E) {
     extern __shared__ float4 policy_net_lds4[];
     float *s_h1 = reinterpret_cast<float *>(policy_net_lds4);
     const int h1s = net_lds_h1_stride(m.N1), xs = net_lds_obs_stride(m.K1), cs = net_lds_chunk_stride();
@@ -139,9 +152,10 @@ __global__ __launch_bounds__(kNetBlock) void policy_net_kernel(const float *__re
     __syncthreads();
     // hidden layer 2 in chunks of kNetChunk outputs (a tile per slot), and the output layer's chains over each chunk
     // the output tile this wavefront keeps, where the layer has that many: one per slot, so act_dim <= kNetMaxAct
-    // (net_spec_check refuses more, and launch_policy_net an image with more)
-    const int otile = slot;
-    const bool has_out = otile < m.N3 / kNetTile;
+    // (net_spec_check refuses more, and launch_policy_net an image with more); the value net's one tile (N3 = 32, of
+    // which column 0 is V) is slot 0's
+    const int otile = ONE_TILE ? 0 : slot;
+    const bool has_out = ONE_TILE ? slot == 0 : otile < m.N3 / kNetTile;
     net_f32x16 out = net_bias(has_out ? img[m.b3 + (size_t)(otile * kNetTile + (lane & 31))] : 0.f);
     const int ng2 = m.K2 / kNetKGroup, ng3 = m.K3 / kNetKGroup;
     for (int c = 0; c < m.N2 / kNetChunk; ++c) {
@@ -159,19 +173,31 @@ __global__ __launch_bounds__(kNetBlock) void policy_net_kernel(const float *__re
                                img4 + m.w3 / 4 + ((size_t)otile * (size_t)ng3 + (size_t)g0) * 64 + lane, n);
         }
     }
+    return {out, e0, rows, rt * kNetTile, otile, has_out};
+}
+
+// The actor over E rows.  obs [E][O], noise [E][A] or null, actions [E][A] (a), env_actions [E][A] or null.
+template <bool TANH>
+__global__ __launch_bounds__(kNetBlock) void policy_net_kernel(const float *__restrict__ img, NetImage m,
+                                                               const float *__restrict__ obs,
+                                                               const float *__restrict__ noise,
+                                                               float *__restrict__ actions,
+                                                               float *__restrict__ env_actions, int64_t E) {
+    const NetTrunk k = net_trunk<TANH>(img, m, obs, E);
+    const int lane = threadIdx.x & (kWave - 1);
     // the output stage, from the accumulators: a and the env action of the rows with an env
-    if (has_out) {
-        const int j = otile * kNetTile + (lane & 31);
+    if (k.has_out) {
+        const int j = k.otile * kNetTile + (lane & 31);
         if (j < m.A) {
             const float lo = img[m.low + j], hi = img[m.high + j], span = img[m.span + j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = rt * kNetTile + net_acc_row(r, lane);
-                if (row < rows) {
-                    const size_t at = (size_t)(e0 + row) * (size_t)m.A + (size_t)j;
+                const int row = k.row0 + net_acc_row(r, lane);
+                if (row < k.rows) {
+                    const size_t at = (size_t)(k.e0 + row) * (size_t)m.A + (size_t)j;
                     float a, env;
                     if (m.output == SNG_MLP_OUT_SQUASH) {
-                        a = tanhf(out[r]);
+                        a = tanhf(k.out[r]);
                         if (noise) {
                             a = a + noise[at];
                             a = a < -1.f ? -1.f : a;
@@ -180,7 +206,7 @@ __global__ __launch_bounds__(kNetBlock) void policy_net_kernel(const float *__re
                         // SB3's unscale_action as numpy rounds it: the product and the sum on their own
                         env = __fadd_rn(lo, __fmul_rn(__fmul_rn(0.5f, __fadd_rn(a, 1.0f)), span));
                     } else {
-                        a = noise ? out[r] + noise[at] : out[r];
+                        a = noise ? k.out[r] + noise[at] : k.out[r];
                         env = a;
                         if (m.clip) {
                             env = a < lo ? lo : a;

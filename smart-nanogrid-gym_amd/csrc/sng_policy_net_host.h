@@ -150,21 +150,7 @@ inline int net_spec_check(const SngMlpNetSpec *s, int obs_dim, int act_dim, std:
 
 // Non-finite weights are refused at upload.
 inline int net_weights_check(const SngMlpNetSpec &s, const SngMlpWeights *w, std::string *why) {
-    auto no = [&](const char *msg) {
-        if (why) *why = msg;
-        return (int)SNG_ERR_INVALID_ARGUMENT;
-    };
-    if (!w || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3) return no("null policy weights");
-    const size_t H1 = (size_t)s.hidden1, H2 = (size_t)s.hidden2;
-    const struct {
-        const float *v;
-        size_t n;
-    } parts[] = {{w->w1, H1 * (size_t)s.obs_dim}, {w->b1, H1}, {w->w2, H2 * H1}, {w->b2, H2},
-                 {w->w3, (size_t)s.act_dim * H2}, {w->b3, (size_t)s.act_dim}};
-    for (const auto &part : parts)
-        for (size_t i = 0; i < part.n; ++i)
-            if (!std::isfinite(part.v[i])) return no("non-finite policy weight");
-    return SNG_OK;
+    return mlp_weights_check(s.obs_dim, s.hidden1, s.hidden2, s.act_dim, "policy", w, why);
 }
 
 // The weights and the spec's bounds into `img` (NetImage::floats floats).
@@ -215,29 +201,17 @@ inline void net_output(const NetImage &m, const float *img, int j, float mean, b
 // be null.
 inline void mlp_net_host(const NetImage &m, const float *img, int64_t rows, const float *obs, const float *noise,
                          float *actions, float *env_actions) {
-    float h1[kNetMaxWidth], h2[kNetMaxWidth];
-    for (int64_t r = 0; r < rows; ++r) {
-        const float *x = obs + (size_t)r * (size_t)m.O;
-        for (int j = 0; j < m.H1; ++j) {
-            float h = img[m.b1 + j];
-            for (int k = 0; k < m.O; ++k) h = std::fmaf(x[k], img[m.w1 + net_weight_at(m.K1, j, k)], h);
-            h1[j] = policy_activate(m.activation, h);
-        }
-        for (int j = 0; j < m.H2; ++j) {
-            float h = img[m.b2 + j];
-            for (int k = 0; k < m.H1; ++k) h = std::fmaf(h1[k], img[m.w2 + net_weight_at(m.K2, j, k)], h);
-            h2[j] = policy_activate(m.activation, h);
-        }
-        for (int j = 0; j < m.A; ++j) {
-            float h = img[m.b3 + j];
-            for (int k = 0; k < m.H2; ++k) h = std::fmaf(h2[k], img[m.w3 + net_weight_at(m.K3, j, k)], h);
+    const size_t w[3] = {m.w1, m.w2, m.w3};
+    const int KP[3] = {m.K1, m.K2, m.K3};
+    mlp_forward_host(
+        m.O, m.H1, m.H2, m.A, m.activation, img, {m.b1, m.b2, m.b3},
+        [&](int l, int j, int k) { return w[l] + net_weight_at(KP[l], j, k); }, rows, obs, [&](int64_t r, int j, float mean) {
             const size_t at = (size_t)r * (size_t)m.A + (size_t)j;
             float a, env;
-            net_output(m, img, j, h, noise != nullptr, noise ? noise[at] : 0.f, &a, &env);
+            net_output(m, img, j, mean, noise != nullptr, noise ? noise[at] : 0.f, &a, &env);
             actions[at] = a;
             if (env_actions) env_actions[at] = env;
-        }
-    }
+        });
 }
 
 }  // namespace sng

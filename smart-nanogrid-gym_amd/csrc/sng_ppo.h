@@ -1,6 +1,8 @@
 // sng_ppo.h -- rollout_gae_kernel: what a PPO update reads beside the trajectory a policy graph left -- the critic's
 // values, the advantages and returns, and the log-probabilities -- in one launch.  Included by sng_kernels.hip only,
-// behind sng_policy.h (policy_chains, policy_activation and the hidden rows' stride are its).
+// behind sng_policy.h (policy_chains, policy_activation and the hidden rows' stride are its).  gae_advantage / gae_step
+// and logp_term, the recurrence's step and the log-probability's term, are defined here for gae_scan_kernel
+// (sng_ppo_net.h) too.
 //
 // The arithmetic is the contract of sng_ppo_host.h.  One workgroup of kPolicyWaves wavefronts owns 64 envs of one
 // day and walks the day backwards, t = T .. 0: the value net over the step's observation tile as policy_kernel runs
@@ -72,6 +74,25 @@ struct RowsStage {
     }
 };
 
+// One step of the recurrence (sng_ppo_host.h, ppo_gae_step): `gae` in, the step's advantage out (the new gae).
+__device__ __forceinline__ float gae_advantage(float g, float gl, float r, float nn, float v, float v_next, float gae) {
+    const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(g, v_next), nn)), v);
+    return __fadd_rn(delta, __fmul_rn(__fmul_rn(gl, nn), gae));
+}
+// ... and the step's return with it: ret = advantage + v.
+__device__ __forceinline__ float gae_step(float g, float gl, float r, float nn, float v, float v_next, float gae,
+                                          float &ret) {
+    const float a = gae_advantage(g, gl, r, nn, v, v_next, gae);
+    ret = __fadd_rn(a, v);
+    return a;
+}
+
+// One term of a row's log-probability (sng_ppo_host.h, ppo_logp_row)
+__device__ __forceinline__ float logp_term(float noise, float inv_std, float log_std) {
+    const float z = __fmul_rn(noise, inv_std);
+    return __fsub_rn(__fsub_rn(__fmul_rn(__fmul_rn(-0.5f, z), z), log_std), kHalfLog2Pi);
+}
+
 // obs [days][T + 1][E][O], reward / done [days][T][E], noise [T][E][A] or null (no log-probability stage), values
 // [days][T + 1][E], advantages / returns / logp [days][T][E].  g, gl: gamma and gamma * lambda (ppo_gamma_f32,
 // ppo_gamma_lambda_f32).  Grid (ceil(E / 64), days).
@@ -88,7 +109,7 @@ __global__ __launch_bounds__(kPolicyBlock) void rollout_gae_kernel(const float *
                                                                    int vec_obs, int vec_noise) {
     extern __shared__ float4 ppo_lds4[];
     constexpr int H = kPolicyHidden, NJ = H / kPolicyWaves;
-    const int O = m.v.O, A = m.A;
+    const int O = m.v.O, A = m.head.A;
     float *s_obs = reinterpret_cast<float *>(ppo_lds4);
     float *s_h = s_obs + (two_tiles ? 2 : 1) * policy_lds_obs(O);
     float *s_nz = s_h + policy_lds_hidden();
@@ -164,8 +185,7 @@ __global__ __launch_bounds__(kPolicyBlock) void rollout_gae_kernel(const float *
             if (live) SNG_ST(values[val_d + (size_t)t * (size_t)E], v);
             if (t < T) {
                 const float r = (float)rw, nn = __fsub_rn(1.0f, (float)dn);
-                const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(g, v_next), nn)), v);
-                gae = __fadd_rn(delta, __fmul_rn(__fmul_rn(gl, nn), gae));
+                gae = gae_advantage(g, gl, r, nn, v, v_next, gae);
                 if (live) {
                     const size_t at = out_d + (size_t)t * (size_t)E;
                     SNG_ST(advantages[at], gae);
@@ -178,12 +198,9 @@ __global__ __launch_bounds__(kPolicyBlock) void rollout_gae_kernel(const float *
             }
             v_next = v;
         } else if (wave == 1 && lp_step && logp != nullptr) {
-            const float *nz = s_nz + lane * A, *ls = wimg + m.log_std, *is = wimg + m.inv_std;
+            const float *nz = s_nz + lane * A, *ls = wimg + m.head.log_std, *is = wimg + m.head.inv_std;
             float lp = 0.0f;
-            for (int j = 0; j < A; ++j) {
-                const float z = __fmul_rn(nz[j], is[j]);
-                lp = __fadd_rn(lp, __fsub_rn(__fsub_rn(__fmul_rn(__fmul_rn(-0.5f, z), z), ls[j]), kHalfLog2Pi));
-            }
+            for (int j = 0; j < A; ++j) lp = __fadd_rn(lp, logp_term(nz[j], is[j], ls[j]));
             if (live) SNG_ST(logp[out_d + (size_t)t * (size_t)E], lp);
         }
         if (two_tiles && t > 0) next_obs.commit(s_nx, tid);

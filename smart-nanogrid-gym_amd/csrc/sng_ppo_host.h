@@ -23,23 +23,36 @@ namespace sng {
 constexpr float kHalfLog2Pi = 0.91893853f;   // 0.5 log(2 pi), float32
 constexpr int32_t kPpoMaxLaunchDays = 65535;   // sng_ppo_finish: the days are the y dimension of one launch's grid
 
-// The device image, in floats: the value net's PolicyImage (A = 1), then log_std and inv_std = 1 / exp(log_std), each
-// padded to a multiple of kPolicyOutChunk with zeros.  inv_std is computed once, on the host, when the image is
-// packed: the device never calls expf, and host and device read the same words.
+// The Gaussian head's part of a head's device image: log_std and inv_std = 1 / exp(log_std), each padded to a
+// multiple of kPolicyOutChunk with zeros, behind the value net's image.  inv_std is computed once, on the host, when the
+// image is packed: the device never calls expf, and host and device read the same words.
+struct GaussHead {
+    int32_t A = 0, AP = 0;
+    size_t log_std = 0, inv_std = 0;
+};
+
+// the head laid out from float `at` of an image on; *floats: the image's size with it
+inline GaussHead gauss_head(int A, size_t at, size_t *floats) {
+    GaussHead h;
+    h.A = A;
+    h.AP = (A + kPolicyOutChunk - 1) / kPolicyOutChunk * kPolicyOutChunk;
+    h.log_std = at;
+    h.inv_std = h.log_std + (size_t)h.AP;
+    *floats = h.inv_std + (size_t)h.AP;
+    return h;
+}
+
+// The device image, in floats: the value net's PolicyImage (A = 1), then the Gaussian head.
 struct PpoImage {
     PolicyImage v;
-    int32_t A = 0, AP = 0;
-    size_t log_std = 0, inv_std = 0, floats = 0;
+    GaussHead head;
+    size_t floats = 0;
 };
 
 inline PpoImage ppo_image(int O, int A, int activation) {
     PpoImage m;
     m.v = policy_image(O, 1, activation, false);
-    m.A = A;
-    m.AP = (A + kPolicyOutChunk - 1) / kPolicyOutChunk * kPolicyOutChunk;
-    m.log_std = m.v.floats;
-    m.inv_std = m.log_std + (size_t)m.AP;
-    m.floats = m.inv_std + (size_t)m.AP;
+    m.head = gauss_head(A, m.v.floats, &m.floats);
     return m;
 }
 
@@ -67,19 +80,15 @@ inline int ppo_log_std_check(int A, const float *log_std, std::string *why) {
     return SNG_OK;
 }
 
-// The value net's weights as policy_weights_check refuses them, and log_std.
-inline int ppo_weights_check(int O, int A, int activation, const SngMlpWeights *w, const float *log_std, std::string *why) {
-    if (int rc = policy_weights_check(ppo_value_spec(O, activation), w, why)) {
-        if (why) *why = (w && w->w1 && w->b1 && w->w2 && w->b2 && w->w3 && w->b3) ? "non-finite value net weight"
-                                                                                : "null value net weights";
-        return rc;
-    }
+// The value net's weights as mlp_weights_check refuses them, and log_std.
+inline int ppo_weights_check(int O, int A, int /*activation*/, const SngMlpWeights *w, const float *log_std, std::string *why) {
+    if (int rc = mlp_weights_check(O, kPolicyHidden, kPolicyHidden, 1, "value net", w, why)) return rc;
     return ppo_log_std_check(A, log_std, why);
 }
 
-// The image of a head without a value net (zero weights): for a caller that brings its own values.
-inline void ppo_pack_log_std(const PpoImage &m, const float *log_std, float *img) {
-    for (size_t i = 0; i < m.floats; ++i) img[i] = 0.f;
+// The image of a head without a value net (zero weights), `floats` floats: for a caller that brings its own values.
+inline void ppo_pack_log_std(const GaussHead &m, size_t floats, const float *log_std, float *img) {
+    for (size_t i = 0; i < floats; ++i) img[i] = 0.f;
     for (int j = 0; j < m.A; ++j) {
         const float ls = log_std ? log_std[j] : 0.f;
         img[m.log_std + j] = ls;
@@ -89,7 +98,7 @@ inline void ppo_pack_log_std(const PpoImage &m, const float *log_std, float *img
 
 // The value net and log_std (null: zeros, SB3's log_std_init) into `img` (PpoImage::floats floats).
 inline void ppo_pack(const PpoImage &m, const SngMlpWeights &w, const float *log_std, float *img) {
-    ppo_pack_log_std(m, log_std, img);
+    ppo_pack_log_std(m.head, m.floats, log_std, img);
     policy_pack(m.v, ppo_value_spec(m.v.O, m.v.activation), w, img);
 }
 
@@ -139,7 +148,7 @@ inline void ppo_gae_host(int32_t days, int32_t T, int64_t E, double gamma, doubl
 }
 
 // One row's log-probability: `noise` [A] under N(0, exp(log_std)), in j order.
-inline float ppo_logp_row(const PpoImage &m, const float *img, const float *noise) {
+inline float ppo_logp_row(const GaussHead &m, const float *img, const float *noise) {
     float lp = 0.0f;
     for (int j = 0; j < m.A; ++j) {
         const float z = noise[j] * img[m.inv_std + j];
@@ -150,7 +159,7 @@ inline float ppo_logp_row(const PpoImage &m, const float *img, const float *nois
 }
 
 // noise [T][E][A], reused every day -> logp [days][T][E]
-inline void ppo_logp_host(const PpoImage &m, const float *img, int32_t days, int32_t T, int64_t E, const float *noise,
+inline void ppo_logp_host(const GaussHead &m, const float *img, int32_t days, int32_t T, int64_t E, const float *noise,
                           float *logp) {
     const size_t rows = (size_t)T * (size_t)E;
     for (int32_t d = 0; d < days; ++d)

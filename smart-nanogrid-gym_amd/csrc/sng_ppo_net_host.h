@@ -2,8 +2,8 @@
 // sng_ppo_create_net): the validation of an SngPpoNetSpec, the head's device image and the contract's arithmetic on
 // the CPU.  Nothing is computed here that another header does not state already: the value path is mlp_net_host
 // (sng_policy_net_host.h) on a NetImage packed by net_pack for (obs_dim, 1, hidden1, hidden2), the advantages are
-// ppo_gae_host and the log-probabilities ppo_logp_host (sng_ppo_host.h), which read log_std / inv_std through a
-// PpoImage whose offsets point behind the NetImage.  value_net_kernel and gae_scan_kernel (sng_ppo_net.h) reproduce
+// ppo_gae_host and the log-probabilities ppo_logp_host (sng_ppo_host.h), which read log_std / inv_std through the
+// GaussHead laid out behind the NetImage.  value_net_kernel and gae_scan_kernel (sng_ppo_net.h) reproduce
 // it by value with relu and up to the device's tanhf with tanh.  Host only, no HIP: it compiles with plain g++
 // (tests/native/ppo_net_host_check.cpp runs it against naive loops); build with -ffp-contract=off.
 #pragma once
@@ -17,13 +17,11 @@
 
 namespace sng {
 
-// The device image, in floats: the value net's NetImage (A = 1, the mean output, no bounds), then log_std and
-// inv_std = 1 / exp(log_std) as PpoImage lays them out (each padded to a multiple of kPolicyOutChunk with zeros;
-// inv_std computed once, on the host, when the image is packed).  `head` is that tail as the PpoImage ppo_logp_host
-// and ppo_pack_log_std take: its log_std / inv_std / floats index the whole image, its `v` is not used.
+// The device image, in floats: the value net's NetImage (A = 1, the mean output, no bounds), then the Gaussian head
+// (sng_ppo_host.h, GaussHead), as in a PpoImage.
 struct PpoNetImage {
     NetImage v;
-    PpoImage head;
+    GaussHead head;
     size_t floats = 0;
 };
 
@@ -37,12 +35,7 @@ inline SngMlpNetSpec ppo_net_value_spec(int O, const SngPpoNetSpec &s) {
 inline PpoNetImage ppo_net_image(int O, int A, const SngPpoNetSpec &s) {
     PpoNetImage m;
     m.v = net_image(O, 1, s.hidden1, s.hidden2, s.activation, SNG_MLP_OUT_MEAN, false);
-    m.head.A = A;
-    m.head.AP = (A + kPolicyOutChunk - 1) / kPolicyOutChunk * kPolicyOutChunk;
-    m.head.log_std = m.v.floats;
-    m.head.inv_std = m.head.log_std + (size_t)m.head.AP;
-    m.head.floats = m.head.inv_std + (size_t)m.head.AP;
-    m.floats = m.head.floats;
+    m.head = gauss_head(A, m.v.floats, &m.floats);
     return m;
 }
 
@@ -68,20 +61,16 @@ inline int ppo_net_spec_check(const SngPpoNetSpec *s, int O, int A, std::string 
     return SNG_OK;
 }
 
-// The value net's weights as net_weights_check refuses them, under ppo_weights_check's messages, and log_std.
+// The value net's weights as mlp_weights_check refuses them, and log_std.
 inline int ppo_net_weights_check(int O, int A, const SngPpoNetSpec &s, const SngMlpWeights *w, const float *log_std,
                                  std::string *why) {
-    if (int rc = net_weights_check(ppo_net_value_spec(O, s), w, why)) {
-        if (why) *why = (w && w->w1 && w->b1 && w->w2 && w->b2 && w->w3 && w->b3) ? "non-finite value net weight"
-                                                                                : "null value net weights";
-        return rc;
-    }
+    if (int rc = mlp_weights_check(O, s.hidden1, s.hidden2, 1, "value net", w, why)) return rc;
     return ppo_log_std_check(A, log_std, why);
 }
 
 // The image of a head without a value net (zero weights): for a caller that brings its own values.
 inline void ppo_net_pack_log_std(const PpoNetImage &m, const float *log_std, float *img) {
-    ppo_pack_log_std(m.head, log_std, img);   // zeros the whole image first
+    ppo_pack_log_std(m.head, m.floats, log_std, img);   // zeros the whole image first
 }
 
 // The value net and log_std (null: zeros) into `img` (PpoNetImage::floats floats).

@@ -47,6 +47,47 @@ SB3_VALUE_KEYS = ("mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0
 SB3_LOG_STD_KEY = "log_std"
 
 
+def _stream_arg(device, stream):
+    """The stream a call runs on: torch's current one of `device`, or the caller's raw handle."""
+    return _stream_handle(device) if stream is None else ctypes.c_void_p(stream)
+
+
+def _want(tensor, name, shape, dtype, device, message=None):
+    """Refuses a tensor that is not contiguous, of this shape and dtype, on this device."""
+    if tuple(tensor.shape) != shape or tensor.dtype != dtype or tensor.device != device or not tensor.is_contiguous():
+        raise ValueError(message or f"{name} must be a contiguous {dtype} tensor {shape} on {device}")
+
+
+class _Handle:
+    """A library handle this object owns: close() destroys it once, __del__ closes.  A handle made for an env batch
+    (_own) is closed by the batch before the batch itself: the library wants it destroyed before its env."""
+    _slot = "_p"          # the attribute that holds the handle, None once closed
+    _destroy = None       # the library's destroy call
+    _sync_first = True    # kernels still running may read the handle's device buffers
+    _closed = None        # what _check_open raises
+
+    def _own(self, venv, handle):
+        setattr(self, self._slot, handle)
+        venv._actors.append(weakref.ref(self))
+
+    def _check_open(self):
+        if getattr(self, self._slot) is None:
+            raise RuntimeError(self._closed)
+
+    def close(self):
+        if getattr(self, self._slot, None):
+            if self._sync_first:
+                torch.cuda.synchronize(self.venv.device)
+            getattr(lib(), self._destroy)(getattr(self, self._slot))
+            setattr(self, self._slot, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _as_f32(x):
     if torch is not None and isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
@@ -138,7 +179,7 @@ def host_actions(obs, weights, activation="tanh", low=None, high=None, noise=Non
     return a, env_a
 
 
-class MlpActor:
+class MlpActor(_Handle):
     """An MLP actor of `venv`'s envs on the device.
 
     activation -- of the hidden layers: "tanh" (SB3's MlpPolicy) or "relu"
@@ -157,7 +198,9 @@ class MlpActor:
     `actor(obs)` maps a device tensor [rows <= num_envs, obs_dim] to the env actions [rows, act_dim] (one kernel
     launch on torch's current stream), so the actor is a policy for evaluate_models and tools/closed_loop_bench.py
     like any torch callable.  `actions(obs, noise)` returns (a, env actions) for the whole batch.  The weights are
-    zero until load()."""
+    zero until load().  close() frees the actor's device image and buffers; graphs captured with the actor must not be
+    launched afterwards."""
+    _destroy = "sng_policy_destroy"
 
     def __init__(self, venv, activation="tanh", clip=True, net_arch=(HIDDEN, HIDDEN), squash=False, net=False):
         if activation not in ACTIVATIONS:
@@ -180,8 +223,7 @@ class MlpActor:
         else:
             spec = _spec(self.obs_dim, self.act_dim, activation, self.low, self.high)
             check(lib().sng_policy_create(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
-        self._p = h
-        venv._actors.append(weakref.ref(self))   # the env batch closes its actors before itself
+        self._own(venv, h)
         E = venv.num_envs
         self.actions_d = torch.zeros((E, self.act_dim), dtype=torch.float32, device=venv.device)
         self.env_actions_d = torch.zeros((E, self.act_dim), dtype=torch.float32, device=venv.device)
@@ -243,21 +285,6 @@ class MlpActor:
         return host_actions(_as_f32(obs), self.weights, self.activation, self.low, self.high,
                             None if noise is None else _as_f32(noise), net_arch=self.net_arch, squash=self.squash,
                             net=self.net)
-
-    def close(self):
-        """Frees the actor's device image and buffers.  Closing the env batch closes its actors first (the library
-        wants a policy destroyed before its env); graphs captured with the actor must not be launched afterwards."""
-        if getattr(self, "_p", None):
-            torch.cuda.synchronize(self.venv.device)
-            lib().sng_policy_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def value_weights(weights, obs_dim, net_arch=None):
     """The value net's six float32 arrays (w1 [h1, obs_dim], b1, w2 [h2, h1], b2, w3 [1, h2], b3 [1]; net_arch =
@@ -354,7 +381,7 @@ def ppo_host_finish(obs, reward, done, weights=None, log_std=None, noise=None, g
     return vals, adv, ret, logp
 
 
-class PpoHead:
+class PpoHead(_Handle):
     """What a PPO update reads beside the trajectory, on the device (include/sng.h, sng_ppo_create): the 64-64 value
     net of SB3's MlpPolicy with the actor's activation, the Gaussian head's log_std, and one kernel
     (rollout_gae_kernel) from a trajectory to critic values, advantages, returns and log-probabilities.  The weights
@@ -364,7 +391,10 @@ class PpoHead:
                 those widths (sng_ppo_create_net), whose finish() is two launches: value_net_kernel on the f32-input
                 MFMA over the trajectory's days (T + 1) E rows as one batch, then gae_scan_kernel.  (64, 64) takes
                 this path too: the same results by value, for cross-checking the two.  Widths whose LDS tiles do
-                not fit a compute unit at this station are refused (NativeError, libsng error -2)."""
+                not fit a compute unit at this station are refused (NativeError, libsng error -2).
+    close() frees the head's device image."""
+    _destroy = "sng_ppo_destroy"
+    _closed = "the PPO head is closed"
 
     def __init__(self, venv, activation="tanh", net_arch=None):
         if activation not in ACTIVATIONS:
@@ -380,8 +410,7 @@ class PpoHead:
         else:
             spec = _native.SngPpoNetSpec(self.net_arch[0], self.net_arch[1], ACTIVATIONS[activation])
             check(lib().sng_ppo_create_net(venv._h, ctypes.byref(spec), ctypes.byref(h)), venv._h)
-        self._p = h
-        venv._actors.append(weakref.ref(self))   # the env batch closes its heads with its actors, before itself
+        self._own(venv, h)
         self._out = {}   # days -> (values, advantages, returns, log_prob)
 
     def load(self, weights, log_std=None):
@@ -389,8 +418,7 @@ class PpoHead:
         the rest is ignored), or six arrays in actor_weights' order with act_dim = 1 (and this head's net_arch) and
         log_std [act_dim] (None: zeros).  They take effect at the next finish()."""
         arrs, ls = head_weights(weights, self.obs_dim, self.act_dim, log_std, self.net_arch)
-        if self._p is None:
-            raise RuntimeError("the PPO head is closed")
+        self._check_open()
         w = _weights_struct(arrs)
         with torch.cuda.device(self.venv.device):
             check(lib().sng_ppo_set_weights(self._p, ctypes.byref(w), ls.ctypes.data_as(_native.c_float_p),
@@ -413,27 +441,27 @@ class PpoHead:
         reward_traj float64 and done_traj uint8 [days, T, E] and the noise [T, E, act_dim] the actor added; without
         noise log_prob is None.  One kernel launch (two for a head with net_arch) on torch's current stream (or
         `stream`), no synchronisation."""
-        if self._p is None:
-            raise RuntimeError("the PPO head is closed")
-        venv = self.venv
-        T, E, dev = venv.timesteps, venv.num_envs, venv.device
+        self._check_open()
+        T, E, dev = self.venv.timesteps, self.venv.num_envs, self.venv.device
         days = int(obs_traj.shape[0])
-
-        def want(x, name, shape, dtype):
-            if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor {shape} on {dev}")
-        want(obs_traj, "obs_traj", (days, T + 1, E, self.obs_dim), torch.float32)
-        want(reward_traj, "reward_traj", (days, T, E), torch.float64)
-        want(done_traj, "done_traj", (days, T, E), torch.uint8)
+        _want(obs_traj, "obs_traj", (days, T + 1, E, self.obs_dim), torch.float32, dev)
+        _want(reward_traj, "reward_traj", (days, T, E), torch.float64, dev)
+        _want(done_traj, "done_traj", (days, T, E), torch.uint8, dev)
         if noise is not None:
-            want(noise, "noise", (T, E, self.act_dim), torch.float32)
+            _want(noise, "noise", (T, E, self.act_dim), torch.float32, dev)
         values, adv, ret, logp = self._outputs(days)
-        r = _rollout_struct(days, gamma, gae_lambda, lambda x: x.data_ptr(), obs_traj, reward_traj, done_traj, noise,
-                            values, adv, ret, None if noise is None else logp)
-        s = _stream_handle(dev) if stream is None else ctypes.c_void_p(stream)
+        if noise is None:
+            logp = None
+        self._finish_into(days, obs_traj, reward_traj, done_traj, noise, gamma, gae_lambda, values, adv, ret, logp, stream)
+        return values, adv, ret, logp
+
+    def _finish_into(self, days, obs, reward, done, noise, gamma, gae_lambda, values, adv, ret, logp, stream):
+        """sng_ppo_finish of `days` days into the caller's output rows; nothing is checked here."""
+        dev = self.venv.device
+        r = _rollout_struct(days, gamma, gae_lambda, lambda x: x.data_ptr(), obs, reward, done, noise, values, adv, ret,
+                            logp)
         with torch.cuda.device(dev):
-            check(lib().sng_ppo_finish(self._p, ctypes.byref(r), s), venv._h)
-        return values, adv, ret, (None if noise is None else logp)
+            check(lib().sng_ppo_finish(self._p, ctypes.byref(r), _stream_arg(dev, stream)), self.venv._h)
 
     def host_finish(self, obs_traj, reward_traj, done_traj, noise=None, gamma=0.99, gae_lambda=0.95, values=None):
         """The host model on numpy arrays or tensors: ppo_host_finish with this head's weights."""
@@ -442,20 +470,6 @@ class PpoHead:
         return ppo_host_finish(_as_f32(obs_traj), _np(reward_traj), _np(done_traj), self.weights, self.log_std,
                                None if noise is None else _as_f32(noise), gamma, gae_lambda, self.activation,
                                None if values is None else _as_f32(values), net_arch=self.net_arch)
-
-    def close(self):
-        """Frees the head's device image.  Closing the env batch closes its heads first."""
-        if getattr(self, "_p", None):
-            torch.cuda.synchronize(self.venv.device)
-            lib().sng_ppo_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _np(x):
     if torch is not None and isinstance(x, torch.Tensor):
@@ -494,7 +508,7 @@ def noise_host_fill(kind, act_dim, timesteps, num_envs, days=1, seed=0, mu=0.0, 
     return out
 
 
-class ActionNoise:
+class ActionNoise(_Handle):
     """The exploration noise of `venv`'s envs, drawn on the device (include/sng.h, sng_noise_create): one kernel fills
     whole days' blocks [T, E, act_dim] from counter-based streams keyed by (seed, global env, action, counter, step), so
     a sharded population draws what one population draws, every block has an exact CPU model (host_fill), and a
@@ -506,7 +520,10 @@ class ActionNoise:
     seed  -- of the streams; the source's own, apart from the env's
     mu, scale -- scalars or [act_dim]; set() replaces them, also between two launches of a captured graph
     theta, dt -- of the OU process (SB3's defaults)
-    `counter` is the number of blocks drawn so far: the next fill starts there.  Reading or setting it synchronises."""
+    `counter` is the number of blocks drawn so far: the next fill starts there.  Reading or setting it synchronises.
+    close() frees the source's device buffers; graphs captured with the source must not be launched afterwards."""
+    _destroy = "sng_noise_destroy"
+    _closed = "the noise source is closed"
 
     def __init__(self, venv, kind="gaussian", seed=0, mu=0.0, scale=1.0, theta=0.15, dt=1e-2):
         self.venv, self.kind, self.seed = venv, kind, int(seed)
@@ -517,16 +534,14 @@ class ActionNoise:
         h = ctypes.c_void_p()
         with torch.cuda.device(venv.device):
             check(lib().sng_noise_create(venv._h, ctypes.byref(self._spec), ctypes.byref(h)), venv._h)
-        self._p = h
-        venv._actors.append(weakref.ref(self))   # the env batch closes its sources with its actors, before itself
+        self._own(venv, h)
         self._out = {}   # days -> tensor
         self.mu = self.scale = None
         self.set(mu, scale)
 
     def set(self, mu, scale):
         """Upload new per-action mu and scale (scalars or [act_dim]); they take effect at the next fill or launch."""
-        if self._p is None:
-            raise RuntimeError("the noise source is closed")
+        self._check_open()
         mu, scale = _per_action(mu, self.act_dim, "mu"), _per_action(scale, self.act_dim, "scale")
         F = _native.c_float_p
         with torch.cuda.device(self.venv.device):
@@ -538,21 +553,19 @@ class ActionNoise:
     def fill(self, days=1, out=None, stream=None):
         """`days` new blocks as a device tensor [days, T, E, act_dim] this source owns (overwritten by the next fill
         of as many days), or into `out`; two launches on torch's current stream (or `stream`), no synchronisation."""
-        if self._p is None:
-            raise RuntimeError("the noise source is closed")
+        self._check_open()
         venv = self.venv
         shape = (int(days), venv.timesteps, venv.num_envs, self.act_dim)
         if out is None:
             if days not in self._out and int(days) >= 1:
                 self._out[days] = torch.empty(shape, dtype=torch.float32, device=venv.device)
             out = self._out.get(days)
-        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != venv.device
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 tensor {shape} on {venv.device}")
-        s = _stream_handle(venv.device) if stream is None else ctypes.c_void_p(stream)
+        else:
+            _want(out, "out", shape, torch.float32, venv.device,
+                  f"out must be a contiguous float32 tensor {shape} on {venv.device}")
         with torch.cuda.device(venv.device):
-            check(lib().sng_noise_fill(self._p, None if out is None else ctypes.c_void_p(out.data_ptr()), int(days), s),
-                  venv._h)
+            check(lib().sng_noise_fill(self._p, None if out is None else ctypes.c_void_p(out.data_ptr()), int(days),
+                                       _stream_arg(venv.device, stream)), venv._h)
         return out
 
     def host_fill(self, days=1, counter=None):
@@ -565,8 +578,7 @@ class ActionNoise:
 
     @property
     def counter(self):
-        if self._p is None:
-            raise RuntimeError("the noise source is closed")
+        self._check_open()
         c = ctypes.c_uint64()
         with torch.cuda.device(self.venv.device):
             check(lib().sng_noise_get_counter(self._p, ctypes.byref(c), _stream_handle(self.venv.device)), self.venv._h)
@@ -574,25 +586,9 @@ class ActionNoise:
 
     @counter.setter
     def counter(self, value):
-        if self._p is None:
-            raise RuntimeError("the noise source is closed")
+        self._check_open()
         with torch.cuda.device(self.venv.device):
             check(lib().sng_noise_set_counter(self._p, int(value), _stream_handle(self.venv.device)), self.venv._h)
-
-    def close(self):
-        """Frees the source's device buffers.  Closing the env batch closes its sources first; graphs captured with
-        the source must not be launched afterwards."""
-        if getattr(self, "_p", None):
-            torch.cuda.synchronize(self.venv.device)
-            lib().sng_noise_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class PpoRollout:
     """A PPO iteration's rollout as one object: `days` closed-loop days (a ClosedLoopGraph with trajectory=True) and
@@ -634,7 +630,6 @@ class PpoRollout:
         else:   # the source's blocks, one per day: [days, T, E, A]
             self.graph = ClosedLoopGraph(venv, actor, noise=noise, days=self.days, with_reset=with_reset, trajectory=True)
             self.noise = self.graph.noise_traj
-            self._day_out = None
         self.values = self.advantages = self.returns = self.log_prob = None
 
     obs = property(lambda self: self.graph.obs_traj)
@@ -668,26 +663,18 @@ class PpoRollout:
                 g.obs_traj, g.reward_traj, g.done_traj, self.noise, self.gamma, self.gae_lambda, stream=stream)
             return
         # one finish per day (sng_ppo_finish with days = 1), on that day's blocks and that day's noise, straight into
-        # day d's rows of this object's [days, ..] outputs
-        venv = self.venv
-        if self._day_out is None:
-            T, E, dev = venv.timesteps, venv.num_envs, venv.device
-            self._day_out = (torch.empty((self.days, T + 1, E), dtype=torch.float32, device=dev),) + tuple(
-                torch.empty((self.days, T, E), dtype=torch.float32, device=dev) for _ in range(3))
-        vals, adv, ret, logp = self._day_out
-        s = _stream_handle(venv.device) if stream is None else ctypes.c_void_p(stream)
-        with torch.cuda.device(venv.device):
-            for d in range(self.days):
-                r = _rollout_struct(1, self.gamma, self.gae_lambda, lambda x: x.data_ptr(), g.obs_traj[d],
-                                    g.reward_traj[d], g.done_traj[d], self.noise[d], vals[d], adv[d], ret[d], logp[d])
-                check(lib().sng_ppo_finish(self.head._p, ctypes.byref(r), s), venv._h)
+        # day d's rows of the head's [days, ..] outputs
+        vals, adv, ret, logp = self.head._outputs(self.days)
+        for d in range(self.days):
+            self.head._finish_into(1, g.obs_traj[d], g.reward_traj[d], g.done_traj[d], self.noise[d], self.gamma,
+                                   self.gae_lambda, vals[d], adv[d], ret[d], logp[d], stream)
         self.values, self.advantages, self.returns, self.log_prob = vals, adv, ret, logp
 
     def close(self):
         self.graph.close()
 
 
-class ClosedLoopGraph:
+class ClosedLoopGraph(_Handle):
     """Whole days with the actor in the loop, captured once as a hipGraph and replayed: ([device-RNG reset] + T x
     (actor, step)) x days (include/sng.h, sng_graph_create_policy).
 
@@ -707,6 +694,7 @@ class ClosedLoopGraph:
                   results; for A/B and tests).  step_nodes wins over it.  An actor on policy_net_kernel (another
                   net_arch, squash) has no fused day: its graphs are nodes whatever is asked.
     New weights loaded into the actor take effect at the next launch, without a recapture."""
+    _slot, _destroy, _sync_first = "_g", "sng_graph_destroy", False
 
     def __init__(self, venv, actor, noise=None, days=1, with_reset=True, trajectory=False, day_returns=None,
                  step_nodes=False, fused=False):
@@ -738,9 +726,8 @@ class ClosedLoopGraph:
         self.day_returns = day_returns
         dr = None
         if day_returns is not None:
-            if (tuple(day_returns.shape) != (self.days, E) or day_returns.dtype != torch.float64
-                    or day_returns.device != venv.device or not day_returns.is_contiguous()):
-                raise ValueError("day_returns must be a contiguous float64 device tensor [days, num_envs]")
+            _want(day_returns, "day_returns", (self.days, E), torch.float64, venv.device,
+                  "day_returns must be a contiguous float64 device tensor [days, num_envs]")
             dr = ctypes.c_void_p(day_returns.data_ptr())
         obs, reward, done = venv.obs_d, venv.reward_d, venv.done_d
         self.obs_traj = self.action_traj = self.reward_traj = self.done_traj = None
@@ -780,22 +767,10 @@ class ClosedLoopGraph:
             raise RuntimeError("the actor was closed: a ClosedLoopGraph needs it for every launch")
         if self.noise_source is not None and self.noise_source._p is None:   # ... and the source's counter
             raise RuntimeError("the noise source was closed: a ClosedLoopGraph needs it for every launch")
-        s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)
         if self.trajectory and not self.with_reset:   # the loaded day's t = 0 observation, ahead of the graph
             if stream is None:
                 self.obs_traj[0, 0].copy_(self.venv.obs_d)
             else:
                 with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.venv.device)):
                     self.obs_traj[0, 0].copy_(self.venv.obs_d)
-        check(lib().sng_graph_launch(self._g, s), self.venv._h)
-
-    def close(self):
-        if getattr(self, "_g", None):
-            lib().sng_graph_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        check(lib().sng_graph_launch(self._g, _stream_arg(self.venv.device, stream)), self.venv._h)

@@ -4,6 +4,11 @@
 #include "sng_host_day.h"
 #include "sng_host_pool.h"
 #include "sng_host_tables.h"
+#include "sng_noise_host.h"
+#include "sng_policy_host.h"
+#include "sng_policy_net_host.h"
+#include "sng_ppo_host.h"
+#include "sng_ppo_net_host.h"
 #include "sng_state_format.h"
 #include "sng_step_plan.h"
 

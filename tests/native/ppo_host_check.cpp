@@ -69,7 +69,7 @@ int main() {
                     ppo_pack(m, w, log_std.data(), img.data());
                     ppo_values_host(m, img.data(), days, T, E, obs.data(), values.data());
                     ppo_gae_host(days, T, E, gamma, lambda, reward.data(), done.data(), values.data(), adv.data(), ret.data());
-                    ppo_logp_host(m, img.data(), days, T, E, noise.data(), logp.data());
+                    ppo_logp_host(m.head, img.data(), days, T, E, noise.data(), logp.data());
                     // the value path: mlp_actor_host with A = 1 on an image of its own, and a naive chain
                     {
                         const SngMlpSpec spec{O, 1, H, activation, nullptr, nullptr};
@@ -133,8 +133,8 @@ int main() {
                             ++checked;
                         }
                     // the image's padding is zero
-                    for (int j = A; j < m.AP; ++j)
-                        if (img[m.log_std + j] != 0.f || img[m.inv_std + j] != 0.f) return 2;
+                    for (int j = A; j < m.head.AP; ++j)
+                        if (img[m.head.log_std + j] != 0.f || img[m.head.inv_std + j] != 0.f) return 2;
                 }
     // validation
     {
