@@ -334,16 +334,24 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
  * need the process's default of 4 hardware queues.  SNG_GRAPH_SERIAL_RESET captures the serial chain (every
  * day's generator, then its steps); SNG_GRAPH_OVERLAPPED_RESET overlaps at every station whose device reset is
  * one launch (about 60 chargers), also where the serial chain measured no slower and is the default (the lean
- * stations, 50 chargers).  The serial flag wins over it, and so do one day and a kept trajectory. */
+ * stations, 50 chargers).  The serial flag wins over it, and so do one day and a kept trajectory.
+ * The default station -- 10 chargers, 1 h steps, PV, BESS, bounded charging, no V2X, no requested SoC, no stochastic
+ * profiles, NumPy-2 promotion -- steps its generated days with day_station_kernel, day_wide_kernel with those
+ * switches fixed at compile time (csrc/sng_step_plan.h, day_station_fixed); the results are the same bit for bit.
+ * SNG_GRAPH_GENERIC_DAY captures day_wide_kernel there too. */
 #define SNG_GRAPH_RESET 1        /* start every day with a device-RNG reset */
 #define SNG_GRAPH_STEP_NODES 2   /* one graph node per step even where a day kernel exists (A/B, tests) */
 #define SNG_GRAPH_TRAJECTORY 4   /* obs / reward / done hold every step of every day (shapes above) */
 #define SNG_GRAPH_SERIAL_RESET 8 /* no generator beside the previous day's steps (A/B, tests) */
 #define SNG_GRAPH_OVERLAPPED_RESET 16 /* ... and beside them at every station whose reset is one launch (A/B, tests) */
 #define SNG_GRAPH_POLICY_FUSED 32 /* sng_graph_create_policy: the fused day wherever it is compiled (A/B, tests) */
+#define SNG_GRAPH_GENERIC_DAY 64 /* day_wide_kernel also where the station-fixed day kernel would run (A/B, tests) */
 int sng_graph_create(SngEnv *env, const float *actions, float *obs, double *reward, uint8_t *done,
                      const SngInfo *info, int flags, int32_t days, double *day_returns, SngGraph **out);
 int sng_graph_launch(SngGraph *graph, void *stream);
+/* The kernel of the graph's day-kernel nodes as rocprofv3 names it, e.g. "void sng::day_station_kernel<10, 2>" or
+ * "void sng::day_wide_kernel<10, 2, false, false>"; an empty string for step nodes and for a policy graph. */
+int sng_graph_day_kernel_name(const SngGraph *graph, char *buf, int32_t len);
 /* Graph nodes that step one day: 1 with the day kernel, else T; a policy graph's node form has 2T (-1 for NULL). */
 int sng_graph_step_nodes(const SngGraph *graph);
 /* 1: the graph generates day d + 1 beside day d's steps (above); 0: the serial chain (-1 for NULL). */

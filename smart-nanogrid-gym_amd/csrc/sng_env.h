@@ -151,6 +151,7 @@ struct SngGraph {
     SngPolicy *policy = nullptr;   // sng_graph_create_policy: the actor between the steps
     bool with_reset = false;
     bool day_kernel = false;   // each day's steps are one day-kernel node (sng_step_day.h), not T step nodes
+    std::string day_kernel_name;   // that node's kernel as rocprofv3 names it (not a policy graph's); else empty
     bool overlapped = false;   // day d + 1 is generated beside day d's steps (sng_step_plan.h reset_overlapped)
     sng::DayKey key{};   // the loaded-day encoding the graph's steps were captured for
     // the stream keys baked into the captured kernels' arguments: the device days a reset graph draws

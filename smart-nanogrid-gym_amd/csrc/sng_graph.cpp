@@ -53,6 +53,13 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
     g->day_kernel = policy ? policy_graph_fused(policy, p, ip, traj, (flags & SNG_GRAPH_STEP_NODES) != 0,
                                                 (flags & SNG_GRAPH_POLICY_FUSED) != 0)
                            : !(flags & SNG_GRAPH_STEP_NODES) && day_kernel_available(p, ip, traj) != 0;
+    // the wide plan's day kernel: the station-fixed one where the plan selects it (sng_step_plan.h
+    // day_station_selected), unless SNG_GRAPH_GENERIC_DAY keeps the generic one
+    const bool generic_day = (flags & SNG_GRAPH_GENERIC_DAY) != 0;
+    if (g->day_kernel && !policy) {
+        char name[128];
+        if (day_kernel_name(p, ip, traj, generic_day, name, (int)sizeof name) > 0) g->day_kernel_name = name;
+    }
     // Overlapped (sng_step_plan.h reset_overlapped, day_shape): the generators are captured on a second stream, day
     // d + 1's into the day slot that day d does not use, so it runs beside day d's steps.  The edges are gen(d) ->
     // day(d), day(d - 1) -> day(d) and day(d - 1) -> gen(d + 1) (the slot is free again); the generators follow
@@ -148,7 +155,7 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
         } else if (g->day_kernel) {
             if (e == hipSuccess)
                 e = launch_day(pd, ds, ipd, actions, obs_d, reward_d, done_d, E, 0, p.T,
-                               (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step);
+                               (vec && aligned16(obs_d)) ? 1 : 0, cs, obs_step, out_step, generic_day);
         } else {
             for (int t = 0; e == hipSuccess && t < p.T; ++t) {
                 float *obs_t = obs_d + (size_t)t * (size_t)obs_step;
@@ -244,6 +251,13 @@ int sng_graph_launch(SngGraph *g, void *stream) {
 int sng_graph_step_nodes(const SngGraph *g) {
     if (!g) return -1;
     return g->day_kernel ? 1 : g->policy ? 2 * g->env->p.T : g->env->p.T;
+}
+
+int sng_graph_day_kernel_name(const SngGraph *g, char *buf, int32_t len) {
+    if (!g || !buf || len < 1) return SNG_ERR_INVALID_ARGUMENT;
+    if ((size_t)len <= g->day_kernel_name.size()) return SNG_ERR_INVALID_ARGUMENT;
+    snprintf(buf, (size_t)len, "%s", g->day_kernel_name.c_str());
+    return SNG_OK;
 }
 
 int sng_graph_reset_overlapped(const SngGraph *g) {

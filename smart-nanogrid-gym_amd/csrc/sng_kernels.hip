@@ -36,7 +36,7 @@
 #include "sng_dev_env.h"        // one env's step arithmetic: charger, BESS, env tail
 #include "sng_step_lean.h"      // step_lean_kernel
 #include "sng_step_wide.h"      // step_wide_kernel
-#include "sng_step_day.h"       // day_wide_kernel, day_lean_kernel
+#include "sng_step_day.h"       // day_wide_kernel, day_station_kernel, day_lean_kernel
 #include "sng_step_general.h"   // step_kernel
 #include "sng_generate.h"       // observe0_kernel, profile_kernel, generate_kernel
 #include "sng_policy.h"         // mlp_actor_tile, policy_kernel
@@ -200,9 +200,10 @@ hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &in
 }
 
 // The day kernel of a plan (day_kernel_of, sng_step_plan.h): day_wide_kernel for the packed days of the wide
-// family's 10-charger station, day_lean_kernel for the lean family's plans (sng_step_day.h); every other plan has
-// none.  N = 50 is not compiled: with every charger's SoC kept next to the step's 239 VGPRs it spills (325-423 VGPR
-// spills, 0.8-1 KB of scratch), so config 5's days stay T step nodes.
+// family's 10-charger station (day_station_kernel where day_station_selected says so), day_lean_kernel for the
+// lean family's plans (sng_step_day.h); every other plan has none.  N = 50 is not compiled: with every charger's
+// SoC kept next to the step's 239 VGPRs it spills (325-423 VGPR spills, 0.8-1 KB of scratch), so config 5's days
+// stay T step nodes.
 typedef void (*DayKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, Params, DeviceState,
                           InfoPtrs);
 typedef void (*DayLeanKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, int64_t, int64_t,
@@ -245,7 +246,7 @@ int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool
 
 hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
                       double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
-                      int64_t obs_step, int64_t out_step) {
+                      int64_t obs_step, int64_t out_step, bool generic_day) {
     const StepPlan pl = step_plan(p, info_diag(info));
     const DayFamily fam = day_kernel_of(pl, obs_step != 0 || out_step != 0);
     if (fam == DAY_NONE) return hipErrorNotSupported;
@@ -253,6 +254,16 @@ hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &inf
     if (fam == DAY_WIDE) {
         DayKernel kern = nullptr;
         const StepLaunch l = day_launch<10>(pl, E, kern);
+        if (day_station_selected(pl, p, generic_day)) {
+            static_assert(kDayStationN == 10 && kWideLanes == 2, "day_launch<10>'s geometry");
+            const DayStationArgs a{act, obs, reward, done, E, t0, nt, vec_io, p.bump_day, p.dt_f, p.ev_power_f, p.ev_eff_f,
+                                   p.dt, p.rdt, p.bess_cap, p.bess_pmax_ch, p.bess_pmax_dis, p.bess_eff_ch,
+                                   p.bess_eff_dis, p.bess_dod, p.grid_w, p.bat_pen_w, p.sell_coef, s.soc, s.bess,
+                                   s.bess0, s.ratio, s.pen0, s.aux, s.flags, s.episode, s.tables, info.flags,
+                                   info.flag_any, info.episode_return};
+            return launch_kernel(day_station_kernel<kDayStationN, kWideLanes>, l.grid, l.block, l.lds, stream, nullptr,
+                                 nullptr, a);
+        }
         return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
                              vec_io, p, s, info);
     }
@@ -271,6 +282,13 @@ hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &inf
     if (obs_step % 4 != 0) vec_io = 0;
     return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
                          vec_io, obs_step, out_step, p, s, info);
+}
+
+int day_kernel_name(const Params &p, const InfoPtrs &info, bool trajectory, bool generic_day, char *buf, int len) {
+    const StepPlan pl = step_plan(p, info_diag(info));
+    if (day_kernel_of(pl, trajectory) == DAY_WIDE && day_station_selected(pl, p, generic_day))
+        return day_station_name(buf, len);
+    return day_plan_name(pl, trajectory, buf, len);
 }
 
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len) {

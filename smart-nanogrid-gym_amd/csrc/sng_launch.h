@@ -26,10 +26,13 @@ hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &in
 // obs_step / out_step: floats from one step's observation block to the next and elements from one step's reward
 // and done block to the next, when every step's outputs are kept (`trajectory`, which only some plans' day
 // kernels can do: sng_step_plan.h day_kernel_of); 0: every step overwrites the same blocks.
+// generic_day: the wide plan's generic kernel also where its station-fixed one would run (sng_step_plan.h).
 int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory = false);
 hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
                       double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
-                      int64_t obs_step = 0, int64_t out_step = 0);
+                      int64_t obs_step = 0, int64_t out_step = 0, bool generic_day = false);
+// The name rocprofv3 reports for the kernel launch_day would launch (an empty string where the plan has none).
+int day_kernel_name(const Params &p, const InfoPtrs &info, bool trajectory, bool generic_day, char *buf, int len);
 hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
                            int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
                            int py = 0);

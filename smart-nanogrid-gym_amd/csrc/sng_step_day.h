@@ -4,6 +4,8 @@
 // no node boundary (1.6-1.9 us each, the end-of-kernel write-back the next node waits for included) and no state
 // round trip.
 //   day_wide_kernel  packed (device-RNG) days of the wide family's 10-charger station, 64 / L envs per wavefront;
+//   day_station_kernel  the same for the default station, its switches fixed at compile time and its arguments
+//                    one small struct (sng_step_plan.h day_station_fixed);
 //   day_lean_kernel  the lean family's stations, packed and unpacked days, 64 envs per wavefront; it can keep every
 //                    step's outputs (per-step strides).
 // Which plan has which is decided in sng_step_plan.h (day_kernel_of).
@@ -67,6 +69,7 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
     const int t1 = t0 + nt;
 #pragma unroll 1
     for (int t = t0; t < t1; ++t) {
+        g.stamp_step_top();
         g.take_step_inputs();
         g.day_tile.commit(lds, lane);
         wave_lds_fence();
@@ -85,6 +88,121 @@ day_wide_kernel(const float *__restrict__ act, float *__restrict__ obs, double *
         g.template run<true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
         wave_lds_fence();   // the next step's tile writes stay behind this step's reads of both tiles
     }
+    SNG_WSTAMP_FLUSH(g.stamp_, 5);   // diagnostic builds: the last step's phases (tools/stamps.py --day)
+    g.store_state(E, p, s, info, lane);
+    bump_day_counter<true>(p, s, t0);
+}
+
+// day_station_kernel: day_wide_kernel<NC, L, false, false> for the one station whose switches are all known when the
+// day is captured (sng_step_plan.h day_station_fixed: the default station of SmartNanogridVecEnv -- PV, BESS, bounded
+// charging, no V2X, NumPy-2 promotion, a power-of-two dt, T = kDayStationT steps, no requested-SoC stream, not a
+// replayed day).  A station's switches never change over the life of a handle, yet the generic kernel holds each in a
+// scalar register through the day (spilled to a VGPR lane and read back: its by-value Params, DeviceState and
+// InfoPtrs are 500-odd bytes) and decides the same select or branch with it on every step.  Here the body's Params
+// is built in the kernel with those switches as constants, which fold through the force-inlined step, and the
+// arguments are one struct of what this path reads: the physical constants of the charger, BESS and cost formulas
+// and the state, record, table and output pointers.  The loop and the geometry are day_wide_kernel's.
+// The per-env flag store, the flag summary and the day return stay run-time pointers (null: not written), as in the
+// generic kernel: every handle of the station takes this kernel, whatever SngInfo it passes.
+// t0 and nt are arguments because they are launch_day's and day_wide_kernel's; launch_day's one caller (a capture,
+// sng_graph.cpp) passes 0 and T, so no part of a day has been run or tested through this kernel.  They were not
+// made constants: that form was not measured.
+struct DayStationArgs {
+    const float *act;
+    float *obs;
+    double *reward;
+    uint8_t *done;
+    int64_t E;
+    int32_t t0, nt, vec_io, bump_day;
+    float dt_f, ev_power_f, ev_eff_f;
+    double dt, rdt;
+    double bess_cap, bess_pmax_ch, bess_pmax_dis, bess_eff_ch, bess_eff_dis, bess_dod;
+    double grid_w, bat_pen_w, sell_coef;
+    double *soc, *bess, *bess0, *ratio, *pen0, *rec;   // rec: the packed records (DeviceState::aux)
+    uint32_t *flags;
+    uint64_t *episode;
+    const Tables *tables;
+    uint32_t *info_flags, *flag_any;   // InfoPtrs::flags, flag_any
+    double *episode_return;
+};
+template <int NC, int L>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) void day_station_kernel(DayStationArgs a) {
+    Params p{};
+    p.n = NC;
+    p.T = kDayStationT;
+    p.act_dim = NC + 1;
+    p.obs_dim = 2 * NC + 9;
+    p.pv = p.bess = p.bounded = p.dt_pow2 = p.packed = 1;   // v2x, legacy, req_stream, req_zero, noise: 0
+    p.lanes = 1;
+    p.bump_day = a.bump_day;
+    p.dt = a.dt;
+    p.rdt = a.rdt;
+    p.dt_f = a.dt_f;
+    p.ev_power_f = a.ev_power_f;
+    p.ev_eff_f = a.ev_eff_f;
+    p.bess_cap = a.bess_cap;
+    p.bess_pmax_ch = a.bess_pmax_ch;
+    p.bess_pmax_dis = a.bess_pmax_dis;
+    p.bess_eff_ch = a.bess_eff_ch;
+    p.bess_eff_dis = a.bess_eff_dis;
+    p.bess_dod = a.bess_dod;
+    p.grid_w = a.grid_w;
+    p.bat_pen_w = a.bat_pen_w;
+    p.sell_coef = a.sell_coef;
+    DeviceState s{};
+    s.soc = a.soc;
+    s.bess = a.bess;
+    s.bess0 = a.bess0;
+    s.ratio = a.ratio;
+    s.pen0 = a.pen0;
+    s.aux = a.rec;
+    s.flags = a.flags;
+    s.episode = a.episode;
+    s.tables = a.tables;
+    InfoPtrs info{};
+    info.flags = a.info_flags;
+    info.flag_any = a.flag_any;
+    info.episode_return = a.episode_return;
+    // day_wide_kernel's loop without the stream and the profile factors, statement for statement.  (As one inlined
+    // function shared with that kernel, its four instantiations allocate differently -- 138 SGPR spills for 121 in the
+    // headline's -- and tests/test_day_kernel_resources.py pins them: profiles/day_station_kernel_ab.txt.)
+    using Grp = WideGroup<NC, L, true, false, false>;
+    using Lay = WideLds<NC, L>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x;
+    float *s_obs = lds + Lay::ACT;
+    Grp g;
+    const int64_t E = a.E;
+    const int t0 = a.t0, vec_io = a.vec_io;
+    const float *__restrict__ act = a.act;
+    float *__restrict__ obs = a.obs;
+    double *__restrict__ reward = a.reward;
+    uint8_t *__restrict__ done = a.done;
+    const int64_t e0 = (int64_t)blockIdx.x * Grp::WENVS;
+    const size_t block = (size_t)E * (size_t)p.act_dim;
+    g.template issue<true, false>(e0, act, E, t0, vec_io, p, s, info, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g.fpv[j] = g.fpr[j] = 1.0;
+    g.issue_step_inputs(act, E, t0, vec_io, p, s, lane);
+    wave_vmem_drain();
+    const int t1 = t0 + a.nt;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        g.stamp_step_top();
+        g.take_step_inputs();
+        g.day_tile.commit(lds, lane);
+        wave_lds_fence();
+        if (t + 1 < t1) g.issue_step_inputs(act + (size_t)(t + 1 - t0) * block, E, t + 1, vec_io, p, s, lane);
+        StepConst k;   // all ten pinned to vector registers, as in the generic kernel's <false, false>
+#pragma unroll
+        for (int i = 0; i < CST_COUNT; ++i) {
+            k.v[i] = step_constant_scalar(s.tables, t, i);
+            asm("" : "+v"(k.v[i]));
+        }
+        g.template run<true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
+        wave_lds_fence();
+    }
+    SNG_WSTAMP_FLUSH(g.stamp_, 5);
     g.store_state(E, p, s, info, lane);
     bump_day_counter<true>(p, s, t0);
 }

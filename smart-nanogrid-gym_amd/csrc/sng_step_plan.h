@@ -103,6 +103,31 @@ inline DayFamily day_kernel_of(const StepPlan &pl, bool trajectory) {
     if (pl.family == STEP_WIDE && pl.pk && pl.lanes == kWideLanes && pl.nc == 10 && !trajectory) return DAY_WIDE;
     return DAY_NONE;
 }
+// Within DAY_WIDE: whether the day runs day_station_kernel<10, 2> (sng_step_day.h), day_wide_kernel<10, 2, false,
+// false> with the station's switches as compile-time constants.  day_station_fixed is true exactly when every fact
+// that kernel fixes holds for the handle: the wide family's packed days at N = 10 without the requested-SoC stream
+// and without stochastic profiles (the plan), and PV, a BESS, bounded charging, no V2X, NumPy-2 promotion, a
+// power-of-two dt, not a replayed day (req_zero: the cleared requests change req_default), the dimensions that
+// follow from N with PV and a BESS -- and T = 24.  The kernel compares t + 1 with the constant for `done`, so another
+// day length is not its station: the 2 h (T = 12) and 15 min (T = 96) days keep a power-of-two dt but go to the
+// generic kernel, as every station that was not measured does (only the 1 h day was, profiles/day_station_kernel_ab.txt).
+// A capture takes the station kernel where the predicate holds and its day measured shorter than the generic
+// kernel's (day_station_faster), unless it asks for the generic one (`generic_day`, SNG_GRAPH_GENERIC_DAY: A/B runs
+// and tests).
+constexpr int kDayStationN = 10, kDayStationT = 24;
+inline bool day_station_fixed(const StepPlan &pl, const Params &p) {
+    return day_kernel_of(pl, false) == DAY_WIDE && pl.nc == kDayStationN && p.n == kDayStationN && !pl.req && !pl.noise &&
+           !p.req_stream && !p.req_zero && !p.noise && p.packed && p.pv && p.bess && p.bounded && !p.v2x && !p.legacy &&
+           p.dt_pow2 && p.T == kDayStationT && p.act_dim == kDayStationN + 1 && p.obs_dim == 2 * kDayStationN + 9;
+}
+constexpr bool day_station_faster() { return true; }
+inline bool day_station_selected(const StepPlan &pl, const Params &p, bool generic_day) {
+    return !generic_day && day_station_faster() && day_station_fixed(pl, p);
+}
+// The name rocprofv3 reports for the station kernel.
+inline int day_station_name(char *buf, int len) {
+    return snprintf(buf, (size_t)len, "void sng::day_station_kernel<%d, %d>", kDayStationN, kWideLanes);
+}
 // The form of a captured day with the MLP actor in the loop (sng_graph_create_policy).  Decided here and nowhere
 // else.  POLICY_NODES: T x (policy_kernel node, step node), the step nodes being the plan's own step kernel.
 // POLICY_FUSED: day_lean_policy_kernel<NC, PK, REQ> (sng_policy.h), the actor between the steps of the plan's lean day

@@ -81,6 +81,8 @@ struct WideGroup {
     uint32_t w[CPL];
     double aux[PK ? 1 : CPL], run_[CPL], req[REQ ? CPL : 1];
     SNG_WSTAMP_DECL;   // diagnostic builds: 0 issue, 1 actions tile staged, 2 chargers, 3 env tail, 4 obs stores issued
+    // the day kernels' stamp 0: the top of a step of their loop (each step overwrites the stamps: the last one's stay)
+    __device__ __forceinline__ void stamp_step_top() { SNG_WSTAMP(0); }
 
     // the (per-lane, uniform) byte offsets of charger j of the lane in a [N][E] u32 plane: the lane's first row
     // (or its last-pair charger's) in the per-lane part, j * E (or (N - 2) * E) in the uniform part

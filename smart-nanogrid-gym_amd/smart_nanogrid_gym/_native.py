@@ -28,6 +28,7 @@ GRAPH_TRAJECTORY = 4   # sng.h SNG_GRAPH_TRAJECTORY
 GRAPH_SERIAL_RESET = 8   # sng.h SNG_GRAPH_SERIAL_RESET
 GRAPH_OVERLAPPED_RESET = 16   # sng.h SNG_GRAPH_OVERLAPPED_RESET
 GRAPH_POLICY_FUSED = 32   # sng.h SNG_GRAPH_POLICY_FUSED
+GRAPH_GENERIC_DAY = 64   # sng.h SNG_GRAPH_GENERIC_DAY
 FLAG_NEGATIVE_DEMAND = 0x1
 FLAG_CHARGING_MODE = 0x2
 FLAG_BESS_SOC_ABOVE_1 = 0x4
@@ -183,6 +184,7 @@ EXPORTS = {
     "sng_graph_launch": (ctypes.c_int, [ctypes.c_void_p, _S]),
     "sng_graph_step_nodes": (ctypes.c_int, [ctypes.c_void_p]),
     "sng_graph_reset_overlapped": (ctypes.c_int, [ctypes.c_void_p]),
+    "sng_graph_day_kernel_name": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),
     "sng_graph_destroy": (None, [ctypes.c_void_p]),
     "sng_time_step_kernels": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int32, c_float_p,

@@ -933,7 +933,7 @@ class EpisodeGraph:
     obs_traj[d, t + 1] is the observation step t returned."""
 
     def __init__(self, venv, actions, with_reset=True, days=1, day_returns=None, step_nodes=False, trajectory=False,
-                 serial_reset=False, overlapped_reset=False):
+                 serial_reset=False, overlapped_reset=False, generic_day=False):
         """days > 1 captures that many consecutive days (each with its reset) in one graph,
         which amortises the graph launch.  day_returns: optional device tensor [days, E] f64;
         day d's returns accumulate into row d (instead of venv.return_d).  A seed left by seed() takes effect
@@ -941,7 +941,9 @@ class EpisodeGraph:
         while a seed waits for the next reset.  serial_reset=True captures every day's reset ahead of its steps
         even where the graph would generate the next day beside them (sng.h SNG_GRAPH_SERIAL_RESET; the same
         results; for A/B and tests); overlapped_reset=True does so at every station it can
-        (SNG_GRAPH_OVERLAPPED_RESET), also where the serial chain is the default."""
+        (SNG_GRAPH_OVERLAPPED_RESET), also where the serial chain is the default.  generic_day=True steps the
+        default station's days with day_wide_kernel where day_station_kernel would run (SNG_GRAPH_GENERIC_DAY; the
+        same results, for A/B and tests); day_kernel_name says which one the graph holds."""
         if with_reset:
             venv._apply_pending_seed()
         elif venv._seeds[0] is not None:
@@ -976,7 +978,8 @@ class EpisodeGraph:
                                          | (_native.GRAPH_STEP_NODES if step_nodes else 0)
                                          | (_native.GRAPH_TRAJECTORY if self.trajectory else 0)
                                          | (_native.GRAPH_SERIAL_RESET if serial_reset else 0)
-                                         | (_native.GRAPH_OVERLAPPED_RESET if overlapped_reset else 0),
+                                         | (_native.GRAPH_OVERLAPPED_RESET if overlapped_reset else 0)
+                                         | (_native.GRAPH_GENERIC_DAY if generic_day else 0),
                                          self.days, dr, ctypes.byref(g)), venv._h)
         self._g = g
 
@@ -984,6 +987,14 @@ class EpisodeGraph:
     def step_nodes_per_day(self):
         """Graph nodes that step one day: 1 with the day kernel, else T."""
         return int(lib().sng_graph_step_nodes(self._g))
+
+    @property
+    def day_kernel_name(self):
+        """The kernel of the graph's day-kernel nodes as rocprofv3 names it (sng_graph_day_kernel_name); an empty
+        string where a day is T step nodes."""
+        buf = ctypes.create_string_buffer(128)
+        check(lib().sng_graph_day_kernel_name(self._g, buf, len(buf)), self.venv._h)
+        return buf.value.decode()
 
     @property
     def reset_overlapped(self):

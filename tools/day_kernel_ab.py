@@ -4,7 +4,7 @@ against T step nodes (SNG_GRAPH_STEP_NODES), in one process, on one box, interle
 
   tools/day_kernel_ab.py [--envs E] [--chargers N] [--time-interval 15min --extended-day --pv-noise s --price-noise s]
                          [--v2x] [--requested-soc] [--rng reference] [--steps-only]
-                         [--days 100] [--graph-days 20] [--warmup 8] [--rounds 3] [--against serial_reset]
+                         [--days 100] [--graph-days 20] [--warmup 8] [--rounds 3] [--against serial_reset | generic_day]
 
 The env, the actions and the graph shape are bench.py's (device-RNG days, `graph-days` days per replay, the day
 return accumulated, no per-env flag array).  Each round replays the step-node graph for `days` days, then the
@@ -14,6 +14,7 @@ build of this source it measures that build the same way.
 A station without a day kernel reports the same form twice (step_nodes_per_day says so).
 --against serial_reset compares another pair of forms the same way: every day's reset ahead of its steps
 (SNG_GRAPH_SERIAL_RESET) against the default, which generates day d + 1 beside day d's steps (reset_overlapped).
+--against generic_day: day_wide_kernel (SNG_GRAPH_GENERIC_DAY) against the default, day_station_kernel at its station.
 --steps-only (implied by --rng reference: a captured reset is device-RNG) times steps-only graphs: one day per
 graph, an eager reset of the handle's RNG mode before every launch and the HIP events around the launch alone (the
 reset keeps the device busy while the host queues the events and the graph, so the interval is the graph's)."""
@@ -45,9 +46,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2024)
-    ap.add_argument("--against", choices=["step_nodes", "serial_reset"], default="step_nodes",
+    ap.add_argument("--against", choices=["step_nodes", "serial_reset", "generic_day"], default="step_nodes",
                     help="the other form: T step nodes per day, or every day's reset ahead of its steps "
-                         "(SNG_GRAPH_SERIAL_RESET) against the default's overlapped reset")
+                         "(SNG_GRAPH_SERIAL_RESET) against the default's overlapped reset, or the generic day kernel "
+                         "(SNG_GRAPH_GENERIC_DAY) against the station-fixed one")
     args = ap.parse_args()
     from smart_nanogrid_gym import EpisodeGraph, SmartNanogridVecEnv
     from smart_nanogrid_gym._native import lib
@@ -83,6 +85,7 @@ def main():
              "default": EpisodeGraph(venv, acts, with_reset=reset, days=D)}
     nodes = {k: v.step_nodes_per_day for k, v in forms.items()}
     overlapped = {k: v.reset_overlapped for k, v in forms.items()}
+    day_kernels = {k: getattr(v, "day_kernel_name", None) for k, v in forms.items()}   # None: a build before the entry
 
     def timed_steps_only(graph):
         total = 0.0
@@ -120,7 +123,7 @@ def main():
     print(json.dumps({"build_id": lib().sng_build_id().decode(), "library": os.environ.get("SNG_LIBRARY", "in-tree"),
                       "envs": E, "chargers": args.chargers, "v2x": args.v2x, "requested_soc": args.requested_soc,
                       "rng": args.rng, "steps_only": steps_only, "kernel": venv.step_kernel_name(),
-                      "T": T, "graph_days": D, "step_nodes_per_day": nodes, "reset_overlapped": overlapped,
+                      "T": T, "graph_days": D, "step_nodes_per_day": nodes, "reset_overlapped": overlapped, "day_kernel": day_kernels,
                       "day_gpu_us_min": best, "env_steps_per_s_min_time": {k: round(E * T / (v * 1e-6)) for k, v in best.items()},
                       f"ratio_{args.against}_over_default": round(best[args.against] / best["default"], 4)}), flush=True)
     for v in forms.values():

@@ -1,7 +1,8 @@
 """Per-workgroup phase timeline of the step kernel (diagnostic build libsng_stamps.so, tools/diag).
 
     make -C tools/diag stamps
-    SNG_LIBRARY=smart-nanogrid-gym_amd/lib/libsng_stamps.so python tools/stamps.py [lanes]
+    SNG_LIBRARY=smart-nanogrid-gym_amd/lib/libsng_stamps.so python tools/stamps.py [lanes] [--v2x]
+    SNG_LIBRARY=smart-nanogrid-gym_amd/lib/libsng_stamps.so python tools/stamps.py --day
 
 lanes 0 (default) times the headline's kernel (step_wide_kernel, two lanes per env, 32 envs per
 one-wavefront workgroup); lanes 1 the lean kernel (64 envs per workgroup).  The stamps add no wait of
@@ -10,6 +11,12 @@ their own (s_memrealtime, 100 MHz, when the workgroup's wavefront reaches the po
 (observation tile complete), 4 = observation stores issued.  The
 kernel's device time per step comes from the HIP-event probe of the same process, so the stretch after
 stamp 4 (store drain + end of kernel) is that time minus the last stamp.
+
+--day: the last step (t = 23) of the default station's captured day, in day_station_kernel and, with
+generic_day=True, in day_wide_kernel (sng_step_day.h; both flush the stamps of their loop's last step): 0 = the
+step's top, 1 = tile committed, the next step's loads issued and the table constants loaded, 2 = chargers done,
+3 = loads drained and env tail done, 4 = observation stores issued.  The last step issues no next step's loads, so
+its drain has nothing to wait for.
 """
 import ctypes
 import os
@@ -87,6 +94,46 @@ def main():
     venv.close()
 
 
+def day_main():
+    L = _native.lib()
+    setter = getattr(L, "sng_debug_set_stamps")
+    setter.argtypes = [ctypes.c_void_p]
+    from smart_nanogrid_gym import EpisodeGraph
+    E, N, T = int(os.environ.get("ENVS", 65536)), 10, 24
+    venv = SmartNanogridVecEnv(E, seed=3, rng="device", number_of_chargers=N, time_interval="1h",
+                               charging_mode="bounded", vehicle_uncharged_penalty_mode="sparse",
+                               pv_system_available_in_model=True, battery_system_available_in_model=True)
+    blocks = (E + 31) // 32   # one wavefront of 32 envs per workgroup; 8 stamp slots per block
+    buf = torch.zeros(blocks * 8, dtype=torch.int64, device="cuda:0")
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    acts = torch.rand((T, E, N + 1), device="cuda:0", generator=g)
+    acts[..., -1] = acts[..., -1] * 2 - 1
+    acts = torch.where(torch.rand(acts.shape, device="cuda:0", generator=g) < 0.2, torch.zeros_like(acts), acts).contiguous()
+    names = ["step top (rel. first WG)", "tile, next loads, constants", "chargers", "drain + env tail", "obs stores issued"]
+    q = lambda x: f"med {np.median(x) / 1e3:6.3f}  p10 {np.percentile(x, 10) / 1e3:6.3f}  p90 {np.percentile(x, 90) / 1e3:6.3f} us"
+    for rounds in range(2):
+        for kw in (dict(generic_day=True), {}):
+            gr = EpisodeGraph(venv, acts, with_reset=True, days=1, **kw)
+            assert gr.step_nodes_per_day == 1
+            assert setter(ctypes.c_void_p(buf.data_ptr())) == 0
+            rows = []
+            for rep in range(6):
+                gr.launch()
+                torch.cuda.synchronize()
+                if rep > 0:
+                    rows.append(buf.view(blocks, 8).cpu().numpy()[:, :5].astype(np.float64) * 10.0)   # ns
+            setter(ctypes.c_void_p(0))
+            ph = np.stack(rows)
+            ph = ph - ph[..., :1].min(axis=1, keepdims=True)
+            print(f"--- {gr.day_kernel_name}, t = {T - 1}, round {rounds}")
+            print(f"{names[0]:30s}", q(ph[..., 0]))
+            for k in range(1, 5):
+                print(f"{names[k]:30s}", q(ph[..., k] - ph[..., k - 1]))
+            print(f"{'step top to stores issued':30s}", q(ph[..., 4] - ph[..., 0]))
+            gr.close()
+    venv.close()
+
+
 def report(ph, ids):
     q = lambda x: f"med {np.median(x) / 1e3:6.3f}  p10 {np.percentile(x, 10) / 1e3:6.3f}  p90 {np.percentile(x, 90) / 1e3:6.3f} us"
     names = ["start (rel. first WG)", "tile + per-env landed", "chargers", "env tail", "obs stores issued"]
@@ -116,4 +163,4 @@ def report(ph, ids):
 
 
 if __name__ == "__main__":
-    main()
+    day_main() if "--day" in sys.argv else main()
