@@ -24,6 +24,19 @@ __device__ __forceinline__ void write_obs_header(float *o, const Params &p, cons
     for (int j = 1; j <= 3; ++j) o[k++] = (float)(pn[j] * fpr[j]);
 }
 
+// The same header for the default station (PV, no stochastic profiles: every factor is 1.0 and x * 1.0 is x), for
+// day_station_kernel: the four price entries do not depend on the env, so the caller has them as float32 already
+// (pnf[j] = (float)price_norm[t + j], the value the product by 1.0 rounds to).
+__device__ __forceinline__ void write_obs_header_station(float *o, const double *irr, const float *pnf, double ratio) {
+    o[0] = (float)(irr[0] * ratio);
+    o[1] = pnf[0];
+#pragma unroll
+    for (int j = 1; j <= 3; ++j) {
+        o[1 + j] = (float)(irr[j] * ratio);
+        o[4 + j] = pnf[j];
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // Counter-based 32-bit hash streams (device generator, stochastic profiles).  The oracle
 // restates mix32 / stream_key / profile_factor bit for bit (oracle/sng_oracle.c).

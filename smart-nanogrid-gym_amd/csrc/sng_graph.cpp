@@ -69,7 +69,8 @@ static int capture_days(SngEnv *env, SngPolicy *policy, const float *actions, co
     // more than it hides: its workgroups ask for generator_lds of dynamic LDS so that fewer of them fit a CU.
     size_t generator_lds = 0;
     g->overlapped = !policy && with_reset && reset_graph_overlapped(p, ip, days, traj, (flags & SNG_GRAPH_SERIAL_RESET) != 0,
-                                                         (flags & SNG_GRAPH_OVERLAPPED_RESET) != 0, &generator_lds) != 0;
+                                                         (flags & SNG_GRAPH_OVERLAPPED_RESET) != 0, &generator_lds,
+                                                         g->day_kernel && !policy, generic_day) != 0;
     DeviceState slots[2] = {env->ds, env->ds};
     hipStream_t gs = nullptr;                      // the generators' stream
     std::vector<hipEvent_t> generated, stepped;   // day d's generator / steps are captured

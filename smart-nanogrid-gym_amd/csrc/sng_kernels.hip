@@ -33,6 +33,7 @@
 
 #include "sng_dev_util.h"       // buffer access, LDS tile stagers, the diagnostic hooks
 #include "sng_dev_sums.h"       // numpy's pairwise sum
+#include "sng_exact_sum.h"      // when a running sum of positive powers is that sum (day_station_kernel)
 #include "sng_dev_env.h"        // one env's step arithmetic: charger, BESS, env tail
 #include "sng_step_lean.h"      // step_lean_kernel
 #include "sng_step_wide.h"      // step_wide_kernel
@@ -237,10 +238,11 @@ int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory)
 }
 
 int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
-                           size_t *generator_lds) {
+                           size_t *generator_lds, bool day_kernel, bool generic_day) {
     const StepPlan pl = step_plan(p, info_diag(info));
     if (!reset_overlapped(pl, p, days, trajectory, serial, force)) return 0;
-    if (generator_lds) *generator_lds = overlapped_generator_lds(pl);
+    const bool station_day = day_kernel && day_kernel_of(pl, trajectory) == DAY_WIDE && day_station_selected(pl, p, generic_day);
+    if (generator_lds) *generator_lds = overlapped_generator_lds(pl, station_day);
     return 1;
 }
 
@@ -261,8 +263,9 @@ hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &inf
                                    p.bess_eff_dis, p.bess_dod, p.grid_w, p.bat_pen_w, p.sell_coef, s.soc, s.bess,
                                    s.bess0, s.ratio, s.pen0, s.aux, s.flags, s.episode, s.tables, info.flags,
                                    info.flag_any, info.episode_return};
-            return launch_kernel(day_station_kernel<kDayStationN, kWideLanes>, l.grid, l.block, l.lds, stream, nullptr,
-                                 nullptr, a);
+            // the two tiles and, behind them, the day's table rows (this kernel alone)
+            return launch_kernel(day_station_kernel<kDayStationN, kWideLanes>, l.grid, l.block,
+                                 l.lds + sizeof(StationRows), stream, nullptr, nullptr, a);
         }
         return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
                              vec_io, p, s, info);

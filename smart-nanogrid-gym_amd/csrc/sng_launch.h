@@ -41,9 +41,10 @@ hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed,
                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int day_delta = 0,
                            size_t min_lds = 0);
 // Whether a reset graph of `days` days over this plan is captured overlapped (sng_step_plan.h reset_overlapped),
-// and then the dynamic LDS its generators ask for at least (overlapped_generator_lds).
+// and then the dynamic LDS its generators ask for at least (overlapped_generator_lds).  day_kernel: the graph's days
+// are day-kernel nodes; generic_day as launch_day's (beside day_station_kernel the generators ask for less).
 int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
-                           size_t *generator_lds);
+                           size_t *generator_lds, bool day_kernel = false, bool generic_day = false);
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
 hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t amount = 1);
 hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,

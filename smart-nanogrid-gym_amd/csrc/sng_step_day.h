@@ -125,6 +125,18 @@ struct DayStationArgs {
     uint32_t *info_flags, *flag_any;   // InfoPtrs::flags, flag_any
     double *episode_return;
 };
+// The day's table rows in the wavefront's LDS, behind its two tiles (launch_day asks for the room): entries
+// t = 0 .. T + 2, what the steps of any part of the day read (step t: irr_norm and price_norm t .. t + 3, pv_power
+// and price t).  Staged once, ahead of the loop; a step reads its ten values by LDS reads at a uniform address
+// (the irradiance as two pairs, the env tail's pv_power and price as one pair, the four price entries as float32).
+// The generic kernel reads them by ten scalar loads in three dependent round trips at the top of every step and
+// copies each to a vector register (profiles/day_station_step_ab.txt).
+struct StationRows {
+    static constexpr int N = kDayStationT + 3;
+    double irr[N];
+    double env[N][2];   // pv_power[t], price[t]
+    float pnf[N + 1];   // (float)price_norm[t]
+};
 template <int NC, int L>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) void day_station_kernel(DayStationArgs a) {
     Params p{};
@@ -163,7 +175,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) v
     info.flags = a.info_flags;
     info.flag_any = a.flag_any;
     info.episode_return = a.episode_return;
-    // day_wide_kernel's loop without the stream and the profile factors, statement for statement.  (As one inlined
+    // day_wide_kernel's loop without the stream and the profile factors, in the station's leaner form: the table
+    // rows staged in LDS, the two input pointers carried from step to step, and run<KEEP, STATION>.  (As one inlined
     // function shared with that kernel, its four instantiations allocate differently -- 138 SGPR spills for 121 in the
     // headline's -- and tests/test_day_kernel_resources.py pins them: profiles/day_station_kernel_ab.txt.)
     using Grp = WideGroup<NC, L, true, false, false>;
@@ -179,27 +192,51 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(L, L))) v
     double *__restrict__ reward = a.reward;
     uint8_t *__restrict__ done = a.done;
     const int64_t e0 = (int64_t)blockIdx.x * Grp::WENVS;
-    const size_t block = (size_t)E * (size_t)p.act_dim;
+    // one step's actions and one record plane: what the loop's two input pointers advance by
+    const size_t block = (size_t)E * (size_t)p.act_dim, plane = (size_t)NC * (size_t)E;
+    const float *act_t = act;
+    const uint16_t *rec_t = packed_records(s) + (size_t)(t0 + 1) * plane;   // step t reads record plane t + 1
+    // the day's table rows, one entry a lane (the lanes past the last entry load and write it again)
+    StationRows *rows = reinterpret_cast<StationRows *>(lds + Lay::ACT + Lay::OBS);
+    const int row_i = lane < StationRows::N ? lane : StationRows::N - 1;
+    const Tables *tb = a.tables;
+    const double row_irr = tb->irr_norm[row_i], row_pn = tb->price_norm[row_i], row_pv = tb->pv_power[row_i],
+                 row_price = tb->price[row_i];
     g.template issue<true, false>(e0, act, E, t0, vec_io, p, s, info, lane);
 #pragma unroll
     for (int j = 0; j < 4; ++j) g.fpv[j] = g.fpr[j] = 1.0;
-    g.issue_step_inputs(act, E, t0, vec_io, p, s, lane);
+    g.issue_step_inputs_at(act_t, rec_t, E, vec_io, lane);
     wave_vmem_drain();
+    rows->irr[row_i] = row_irr;
+    rows->pnf[row_i] = (float)row_pn;
+    rows->env[row_i][0] = row_pv;
+    rows->env[row_i][1] = row_price;
+    wave_lds_fence();
     const int t1 = t0 + a.nt;
 #pragma unroll 1
     for (int t = t0; t < t1; ++t) {
         g.stamp_step_top();
+        // this step's ten table values from the staged rows, straight into vector registers: issued here, ahead of
+        // the tile commit, and waited for (lgkmcnt) where the header and the env tail read them.  No scalar load, no
+        // wait on one and no copy from scalar registers in the loop
+        StepConst k;
+        StationStep st;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            k.v[CST_IRR + j] = rows->irr[t + j];
+            k.v[CST_PN + j] = 0.0;   // not read: the header takes st.pnf
+            st.pnf[j] = rows->pnf[t + j];
+        }
+        k.v[CST_PV] = rows->env[t][0];
+        k.v[CST_PRICE] = rows->env[t][1];
+        st.rec_t = rec_t;
         g.take_step_inputs();
         g.day_tile.commit(lds, lane);
         wave_lds_fence();
-        if (t + 1 < t1) g.issue_step_inputs(act + (size_t)(t + 1 - t0) * block, E, t + 1, vec_io, p, s, lane);
-        StepConst k;   // all ten pinned to vector registers, as in the generic kernel's <false, false>
-#pragma unroll
-        for (int i = 0; i < CST_COUNT; ++i) {
-            k.v[i] = step_constant_scalar(s.tables, t, i);
-            asm("" : "+v"(k.v[i]));
-        }
-        g.template run<true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane);
+        act_t += block;
+        rec_t += plane;
+        if (t + 1 < t1) g.issue_step_inputs_at(act_t, rec_t, E, vec_io, lane);
+        g.template run<true, true>(lds, s_obs, obs, reward, done, E, t, vec_io, k, p, s, info, lane, &st);
         wave_lds_fence();
     }
     SNG_WSTAMP_FLUSH(g.stamp_, 5);

@@ -185,6 +185,14 @@ inline bool reset_overlapped(const StepPlan &pl, const Params &p, int days, bool
 // family's day is one wavefront per SIMD and was shorter beside the uncapped generator (N = 8: 114.9 us, capped
 // 117.2 - 118.3), so a forced overlap there is not capped.
 inline size_t overlapped_generator_lds(const StepPlan &pl) { return pl.family == STEP_WIDE ? 56u * 1024u : 0u; }
+// The same beside day_station_kernel (station_day: the graph's days run that kernel), which stages its table rows
+// behind its tiles: 5,880 B a wavefront, 6,400 B as a CU allocates LDS (blocks of 1,280 B), and eight of those fit a
+// CU's 160 KB beside two generator workgroups of up to 55 KB.  Measured beside that kernel, device time per day
+// (profiles/day_station_step_ab.txt): 56 KB 87.0 us (a CU holds seven of the day's wavefronts), 54 KB 76.1 - 77.3,
+// 52 KB 86.0 - 87.1 (three generator workgroups fit a CU where they arrive first).
+inline size_t overlapped_generator_lds(const StepPlan &pl, bool station_day) {
+    return station_day ? 54u * 1024u : overlapped_generator_lds(pl);
+}
 // Day d of `days` in such a graph: the day slot it is generated into and stepped in (0: the handle's own
 // buffers, 1: the shadow's -- the last day is always in slot 0, so after a replay the loaded day is where every
 // other call expects it); the day index its generator draws, as an offset from the day counter at launch (the

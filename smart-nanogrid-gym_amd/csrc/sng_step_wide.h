@@ -28,6 +28,12 @@ namespace sng {
 //     actions and observation tiles (40 KB per wavefront: four per CU).
 // ---------------------------------------------------------------------------------
 
+// What day_station_kernel hands its step besides the StepConst (WideGroup::run<KEEP, STATION>).
+struct StationStep {
+    float pnf[4];            // (float)price_norm[t .. t + 3]: the observation's four price entries, the same for every env
+    const uint16_t *rec_t;   // record plane t + 1
+};
+
 template <int NC, int L>
 struct WideLds {
     static constexpr int WENVS = kWave / L;   // envs per wavefront
@@ -213,6 +219,17 @@ struct WideGroup {
             for (int j = 0; j < CPL; ++j) reqn[j] = bld(s.req + plane, 2u * row_of(j), 2u * r4_of(j, E));
         }
     }
+    // The same for day_station_kernel, whose loop carries the step's actions block and record plane (t + 1) as
+    // pointers it advances, instead of rebuilding both from E, t and t0 by 64-bit scalar multiplies on every step.
+    __device__ __forceinline__ void issue_step_inputs_at(const float *act_t, const uint16_t *rec_t, int64_t E, int vec_io,
+                                                         int lane) {
+        static_assert(PK && !REQ, "the default station's packed days");
+        day_tile.issue(act_t + e0 * Lay::A, nw * Lay::A, vec_io != 0, lane);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            rq[q] = bld(reinterpret_cast<const uint64_t *>(rec_t), rec_a, (uint32_t)(4 * q) * (uint32_t)E * 2u);
+        rl = bld16(rec_t, rec_b, (uint32_t)(NC - 2) * (uint32_t)E * 2u);
+    }
     __device__ __forceinline__ void take_step_inputs() {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) unpack_quad(rq[q], w + 4 * q);
@@ -231,16 +248,22 @@ struct WideGroup {
     // KEEP (the day kernel): what the next step of the same env would load straight back stays in registers --
     // every charger's new SoC in run_[], the BESS SoC in bess_l, the day return in ret_l -- and the caller
     // stores it after the day's last step (store_state); every other output is stored as always.
-    template <bool KEEP = false>
+    // STATION (day_station_kernel, with KEEP): the leaner forms of that kernel's step, each behind this switch so
+    // that every other kernel's step is the code it was.  `st` carries what its caller has per step; k holds the
+    // irradiance entries and the env tail's two constants (its price_norm entries are not read).
+    template <bool KEEP = false, bool STATION = false>
     __device__ __forceinline__ void run(const float *s_act, float *s_obs, float *obs, double *reward, uint8_t *done,
                                         int64_t E, int t, int vec_io, const StepConst &k, const Params &p,
-                                        const DeviceState &s, const InfoPtrs &info, int lane) {
+                                        const DeviceState &s, const InfoPtrs &info, int lane,
+                                        const StationStep *st = nullptr) {
+        static_assert(!STATION || (KEEP && PK && !REQ && !NOISE && kNonneg), "the default station's day kernel");
         SNG_WSTAMP(1);
         const int Ad = p.act_dim, O = p.obs_dim;
         const int le = lane / L, part = lane % L;
         const bool leader = part == 0;
         const size_t plane = (size_t)t * NC * (size_t)E;
         const uint16_t *rec_t = packed_records(s) + plane + (size_t)NC * (size_t)E;
+        if constexpr (STATION) rec_t = st->rec_t;   // carried by the day's loop, not rebuilt from E and t
         const float *a_row = s_act + le * Ad;
         float *o_row = s_obs + le * O;
         float av[CPL];
@@ -260,7 +283,8 @@ struct WideGroup {
         // chargers' loads are still in flight (the BESS's division no longer trails the charger sums)
         BessStep bs{};
         if (live && leader) {
-            write_obs_header(o_row, p, k.v + CST_IRR, k.v + CST_PN, ratio, fpv, fpr);
+            if constexpr (STATION) write_obs_header_station(o_row, k.v + CST_IRR, st->pnf, ratio);
+            else write_obs_header(o_row, p, k.v + CST_IRR, k.v + CST_PN, ratio, fpv, fpr);
             bs = bess_step<!KEEP>(p, s, el8, t, p.bess ? bess_l : 0.0, bess_action);
             if (p.bess) o_row[O - 1] = (float)bs.bess;
         }
@@ -272,6 +296,9 @@ struct WideGroup {
             // charger discharges (charger_step<..., NONNEG>)
             double seq_pos = 0.0, pmin = __builtin_inf();
             int n_pos = 0;
+            // STATION: the exact-sum test on the terms' high words instead of the count, the minimum and the
+            // comparison in f64 (sng_exact_sum.h)
+            uint32_t bmax = kExactSumBmax0, bmin = kExactSumBmin0;
             double qv[CPL], sv[CPL];
             if (live) {
 #pragma unroll
@@ -295,10 +322,15 @@ struct WideGroup {
                     // the lane's own penalties in charger order; the last pair's come after the other lane's
                     // whole pairs (below)
                     if (j < H) pen_v += r.q;
-                    const bool ip = r.pw > 0.0;
-                    seq_pos += r.pw;   // >= 0 here (the float32 product of a >= 0, or 0.0): adding it is exact
-                    n_pos += ip ? 1 : 0;
-                    pmin = __builtin_fmin(pmin, ip ? r.pw : __builtin_inf());
+                    if constexpr (STATION) {
+                        seq_pos += r.pw;
+                        exact_sum_track(exact_sum_hi(r.pw), bmax, bmin);
+                    } else {
+                        const bool ip = r.pw > 0.0;
+                        seq_pos += r.pw;   // >= 0 here (the float32 product of a >= 0, or 0.0): adding it is exact
+                        n_pos += ip ? 1 : 0;
+                        pmin = __builtin_fmin(pmin, ip ? r.pw : __builtin_inf());
+                    }
                     // chargers in order: charger j waits only for its own loads.  A/B of scheduling groups
                     // (profiles/r03_ab_wide_sched_groups.txt): config 5 22.6-22.7 us with one or two chargers
                     // per group, 22.8 with five, 27.1 with no barrier in a lane's 25 chargers; the headline
@@ -318,28 +350,38 @@ struct WideGroup {
             const int n_own = n_pos;
             const uint32_t nx_own = n_nonexist, fl_own = fl;
             int with_pos = n_own > 0 ? 1 : 0;
+            const uint32_t bmax_own = bmax, bmin_own = bmin;
             auto gather = [&] {
-                const int nk = (int)from_part<1>((uint32_t)n_own);
-                with_pos += nk > 0 ? 1 : 0;
-                n_pos += nk;
-                seq_pos += from_part<1>(seq_own);
-                pmin = __builtin_fmin(pmin, from_part<1>(pmin_own));
+                if constexpr (STATION) {
+                    bmax = __builtin_elementwise_max(bmax, from_part<1>(bmax_own));
+                    bmin = __builtin_elementwise_min(bmin, from_part<1>(bmin_own));
+                    seq_pos += from_part<1>(seq_own);
+                } else {
+                    const int nk = (int)from_part<1>((uint32_t)n_own);
+                    with_pos += nk > 0 ? 1 : 0;
+                    n_pos += nk;
+                    seq_pos += from_part<1>(seq_own);
+                    pmin = __builtin_fmin(pmin, from_part<1>(pmin_own));
+                }
                 n_nonexist += from_part<1>(nx_own);
                 fl |= from_part<1>(fl_own);
 #pragma unroll
                 for (int j = 0; j < H; ++j) {
                     const double qk = from_part<1>(qv[j]);
-                    pen_v = leader ? pen_v + qk : pen_v;
+                    // only the leader's pen_v is read (the env tail): STATION adds on both lanes, no select
+                    pen_v = (STATION || leader) ? pen_v + qk : pen_v;
                 }
             };
             gather();
             {   // the last pair: charger N - 2 (this lane), then N - 1 (the other)
                 const double qk = from_part<1>(qv[H]);
-                pen_v = leader ? (pen_v + qv[H]) + qk : pen_v;
+                pen_v = (STATION || leader) ? (pen_v + qv[H]) + qk : pen_v;
             }
             const bool split = with_pos > 1;
             p_ch = seq_pos;
-            const bool pos_slow = live && leader && (n_pos >= 8 || split) && !(seq_pos <= pmin * 0x1.0p28);
+            bool pos_slow;
+            if constexpr (STATION) pos_slow = live && leader && exact_sum_rebuild(bmax, bmin);
+            else pos_slow = live && leader && (n_pos >= 8 || split) && !(seq_pos <= pmin * 0x1.0p28);
             if (__builtin_amdgcn_ballot_w64(pos_slow)) {   // wave-uniform: rare
                 if (pos_slow) {
                     // the compacted positive powers again, in charger order: an occupied charger charging with
