@@ -655,6 +655,121 @@ int sng_graph_create_policy_noise(SngEnv *env, SngPolicy *policy, SngNoise *nois
                                   float *actions_out, double *reward, uint8_t *done, const SngInfo *info, int flags,
                                   int32_t days, double *day_returns, SngGraph **out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The off-policy side of DDPG / TD3 (solvers/RL/ddpg_train.py): a replay ring of whole days, its sampler, the critic
+ * Q(s, a) and the TD targets -- everything between "a closed-loop day ended" and "the caller holds a minibatch and its
+ * targets", on the device, each with an exact host model (csrc/sng_ddpg_host.h).  The gradient step and the polyak
+ * update stay the caller's, who uploads the weights they give, as with PPO.
+ *
+ * Replay ring.  capacity_days slots, each one day of a policy graph's SNG_GRAPH_TRAJECTORY outputs, in device storage
+ * the caller provides at create and keeps alive until destroy (as a graph's outputs are the caller's):
+ *     obs     [capacity_days][T + 1][num_envs][obs_dim] f32
+ *     actions [capacity_days][T][num_envs][act_dim]     f32   the stored a: for a squashed actor the [-1, 1] action,
+ *                                                             which is what SB3's ReplayBuffer stores
+ *     reward  [capacity_days][T][num_envs]              f32   (float)reward: SB3's buffer is float32
+ *     done    [capacity_days][T][num_envs]              u8
+ * A push of `days` days (1 <= days <= capacity_days; more is refused) writes slots head, head + 1, .. (mod
+ * capacity_days) in one launch, then head advances by days (mod capacity_days) and filled = min(filled + days,
+ * capacity_days); both start at 0.  Transition i < n = filled * T * num_envs is
+ *     (slot, t, e) = (i / (T * num_envs), (i / num_envs) % T, i % num_envs)
+ * in physical slot order.  Its next observation is obs[slot][t + 1][e]; for t = T - 1 that is the day's terminal
+ * observation, which the trajectory holds in block T (the next day's reset is in the next slot's block 0).  done is
+ * terminal (the env reports no truncation), so there is no timeout mask.
+ *
+ * Sampling law, in integer operations only, so the device equals the host (sng_replay_host_indices) bit for bit.  Row b
+ * of the sample with counter c takes
+ *     key = mix32(mix32(day_key(seed, c) ^ lo32(off)) ^ (hi32(off) * 0x85ebca6b + 0x72730000 * 0xc2b2ae35 + 0x27d4eb2f))
+ *     kb  = mix32(mix32(key ^ lo32(b)) ^ (hi32(b) * 0x85ebca6b + 0x165667b1))
+ *     h   = (uint64)mix32(kb + 0x9e3779b9) << 32 | mix32(kb + 2 * 0x9e3779b9)
+ *     index = (h * n) >> 64        the high word of the 128-bit product; the bias is below n / 2^64
+ * with mix32 and day_key the action noise's (noise_mix32, noise_day_key), off the env offset when the call is enqueued
+ * and 0x72730000 the sampler's own domain tag.  One text is compiled for both sides.  The counter is a host-side
+ * uint64 of the handle, 0 at create, read by a sample call and bumped by one per sample call; sng_replay_get_counter /
+ * sng_replay_set_counter read and set it without touching the device.  A sample captured into the caller's own graph
+ * therefore repeats itself: its counter was baked into the captured launch.
+ *
+ * Sample output: SB3's ReplayBufferSamples as dense device arrays -- obs [batch][obs_dim], actions [batch][act_dim],
+ * next_obs [batch][obs_dim], reward [batch] f32, done [batch] f32 (0.0 / 1.0) and, where given, index [batch] i64.
+ * Sampling an empty ring or batch < 1 is refused.
+ *
+ * Critic.  Q(s, a) is SngMlpNetSpec's arithmetic with obs_dim := obs_dim + act_dim, act_dim := 1, SNG_MLP_OUT_MEAN, no
+ * noise and no clip, on the input row x = [obs row | action row]: every output is the k-ordered float32 fmaf chain
+ * started from the bias; SngMlpWeights holds w1 [hidden1][obs_dim + act_dim], w2 [hidden2][hidden1], w3 [1][hidden2].
+ * The device (q_net_kernel, csrc/sng_ddpg.h: policy_net_kernel's trunk with its rows staged from two arrays) may append
+ * zero terms to a chain, so device and host are compared by value (==), as value_net_kernel's values are: equal with
+ * relu, equal up to the device's tanhf with tanh.  The refusals are net_spec_check's for that input width, and the
+ * message names the sizes: widths outside 8 .. 512 and LDS tiles above a compute unit's 160 KB are SNG_ERR_UNSUPPORTED
+ * (at 50 chargers the input width is 160: 400-300 needs 147,968 B and fits, 512-512 needs 172,544 B and does not).
+ *
+ * TD target: SB3's TD3.train with n_critics = 1 and no target-policy noise, each float32 operation rounded on its own:
+ *     a' = the target actor's stored action for next_obs   (SNG_MLP_OUT_SQUASH: tanh(mean); no noise)
+ *     q' = Q_target(next_obs, a')
+ *     nn = 1.0f - done;   y = reward + ((nn * (float)gamma) * q')
+ * gamma must be finite and in [0, 1].  Given the device's a' the device's y equals the host's by value with relu.
+ *
+ * Every device call below is asynchronous on `stream`, and none allocates or synchronises after create.  Row counts and
+ * offsets are 64-bit.  Handles are destroyed before their env. */
+typedef struct SngReplaySpec {
+    int32_t capacity_days;          /* >= 1 */
+    uint64_t seed;                  /* of the sampler's streams */
+    float *obs, *actions, *reward;  /* device storage, shapes above */
+    uint8_t *done;
+} SngReplaySpec;
+typedef struct SngReplayBatch {     /* device pointers */
+    float *obs, *actions, *next_obs;    /* [batch][obs_dim], [batch][act_dim], [batch][obs_dim] */
+    float *reward, *done;               /* [batch] */
+    int64_t *index;                     /* [batch] or NULL */
+} SngReplayBatch;
+typedef struct SngReplay SngReplay;
+int sng_replay_create(SngEnv *env, const SngReplaySpec *spec, SngReplay **out);
+/* `days` days of a trajectory -- obs [days][T + 1][num_envs][obs_dim], actions [days][T][num_envs][act_dim], reward f64
+ * and done u8 [days][T][num_envs], device pointers -- into the ring: one launch (replay_push_kernel). */
+int sng_replay_push(SngReplay *ring, int32_t days, const float *obs, const float *actions, const double *reward,
+                    const uint8_t *done, void *stream);
+/* filled * T * num_envs: the transitions a sample draws from (with NULL: 0) */
+int64_t sng_replay_size(const SngReplay *ring);
+/* The slot the next pushed day goes to, and the slots that hold a day. */
+int sng_replay_state(const SngReplay *ring, int32_t *head, int32_t *filled);
+/* One launch (replay_sample_kernel) with the handle's counter, which is then bumped. */
+int sng_replay_sample(SngReplay *ring, int64_t batch, const SngReplayBatch *out, void *stream);
+int sng_replay_get_counter(const SngReplay *ring, uint64_t *out);
+int sng_replay_set_counter(SngReplay *ring, uint64_t counter);
+void sng_replay_destroy(SngReplay *ring);
+/* Host only: the `batch` indices a sample with this seed, env offset and counter draws from n transitions. */
+int sng_replay_host_indices(uint64_t seed, int64_t env_offset, uint64_t counter, uint64_t n, int64_t batch,
+                            int64_t *out);
+
+typedef struct SngCriticSpec {
+    int32_t hidden1, hidden2;      /* each 8 .. 512, any integer */
+    int32_t activation;            /* hidden layers: 0 tanh, 1 relu */
+} SngCriticSpec;
+typedef struct SngCritic SngCritic;
+/* A critic for `env` (its obs_dim and act_dim); the weights are zero until sng_critic_set_weights. */
+int sng_critic_create(SngEnv *env, const SngCriticSpec *spec, SngCritic **out);
+/* Upload into the critic's device image, asynchronously on `stream`: new weights between two calls change the next. */
+int sng_critic_set_weights(SngCritic *critic, const SngMlpWeights *weights, void *stream);
+/* obs [rows][obs_dim], actions [rows][act_dim] -> out [rows]: one launch (q_net_kernel). */
+int sng_critic_q(SngCritic *critic, int64_t rows, const float *obs, const float *actions, float *out, void *stream);
+/* The TD targets of `rows` transitions: two launches, the target actor (policy_net_kernel) over next_obs into
+ * next_actions [rows][act_dim], which is written, then q_net_kernel with the target stage over (next_obs, next_actions)
+ * and reward / done [rows] f32 into y [rows].  actor_target is a policy made by sng_policy_create_net for the same env. */
+int sng_critic_targets(SngCritic *q_target, SngPolicy *actor_target, int64_t rows, const float *next_obs,
+                       const float *reward, const float *done, double gamma, float *next_actions, float *y,
+                       void *stream);
+void sng_critic_destroy(SngCritic *critic);
+/* Host only: the same contracts on host arrays.  Validate as the device calls do.  next_actions_given != 0:
+ * next_actions is read, not computed (actor_spec and actor_weights may then be NULL). */
+int sng_critic_host_q(int32_t obs_dim, int32_t act_dim, const SngCriticSpec *spec, const SngMlpWeights *weights,
+                      int64_t rows, const float *obs, const float *actions, float *out);
+int sng_critic_host_targets(int32_t obs_dim, int32_t act_dim, const SngCriticSpec *spec, const SngMlpWeights *weights,
+                            const SngMlpNetSpec *actor_spec, const SngMlpWeights *actor_weights, int64_t rows,
+                            const float *next_obs, const float *reward, const float *done, double gamma,
+                            float *next_actions, int next_actions_given, float *y);
+/* sng_policy_actions over `rows` rows instead of the env's num_envs: one policy_net_kernel launch.  A policy not made
+ * by sng_policy_create_net is refused (SNG_ERR_UNSUPPORTED). */
+int sng_policy_actions_rows(SngPolicy *policy, int64_t rows, const float *obs, const float *noise, float *actions,
+                            float *env_actions, void *stream);
+
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for
  * `num_envs` envs seeded seed+i; `episode` = number of days already drawn. */

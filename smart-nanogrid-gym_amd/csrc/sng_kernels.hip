@@ -45,6 +45,7 @@
 #include "sng_ppo.h"            // rollout_gae_kernel
 #include "sng_ppo_net.h"        // value_net_kernel, gae_scan_kernel
 #include "sng_noise.h"          // action_noise_kernel
+#include "sng_ddpg.h"           // replay_push_kernel, replay_sample_kernel, q_net_kernel
 
 namespace sng {
 
@@ -625,6 +626,54 @@ hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(noise_bump_kernel, dim3(1), dim3(1), 0, stream, counter, (uint64_t)days);
     return hipGetLastError();
+}
+
+// grid x over the longest segment's 16-byte groups, kPushPer a thread (the others' threads run out of work sooner), y
+// over the segments
+hipError_t launch_replay_push(const PushArgs &a, hipStream_t stream) {
+    if (a.count < 1 || a.count > kPushSegments || a.longest < 1) return hipErrorInvalidValue;
+    for (int i = 0; i < a.count; ++i)
+        if (!a.seg[i].src || !a.seg[i].dst || a.seg[i].n < 1) return hipErrorInvalidValue;
+    const int64_t per = (int64_t)kPushBlock * kPushPer * 4;   // elements of a workgroup, at 4-byte elements
+    int64_t blocks = (a.longest + per - 1) / per;
+    blocks = blocks < 1 ? 1 : blocks > (1 << 20) ? (1 << 20) : blocks;
+    return launch_kernel(replay_push_kernel, dim3((unsigned)blocks, (unsigned)a.count), dim3(kPushBlock), 0, stream,
+                         nullptr, nullptr, a);
+}
+
+hipError_t launch_replay_sample(const ReplayStorage &ring, const SngReplayBatch &out, uint32_t key, uint64_t n, int T,
+                                int64_t E, int O, int A, int64_t batch, hipStream_t stream) {
+    if (batch < 1 || n < 1 || T < 1 || E < 1 || O < 1 || A < 1 || !ring.obs || !ring.actions || !ring.reward ||
+        !ring.done || !out.obs || !out.actions || !out.next_obs || !out.reward || !out.done)
+        return hipErrorInvalidValue;
+    const int64_t blocks = (batch + kSampleRows - 1) / kSampleRows;
+    if (blocks > 2147483647ll || (int64_t)kSampleRows * (O > A ? O : A) > 2147483647ll) return hipErrorInvalidValue;
+    return launch_kernel(replay_sample_kernel, dim3((unsigned)blocks), dim3(kSampleBlock), 0, stream, nullptr, nullptr,
+                         ring, out, key, n, (uint64_t)T * (uint64_t)E, (uint64_t)E, O, A, batch);
+}
+
+// q_net_kernel's dynamic-LDS limit, raised once as ppo_net_kernels_init raises value_net_kernel's: the same tiles.
+hipError_t critic_kernels_init() {
+    static const hipError_t set =
+        raise_lds_limit((int)kNetMaxLds, q_net_kernel<false, false>, q_net_kernel<false, true>,
+                        q_net_kernel<true, false>, q_net_kernel<true, true>);
+    return set;
+}
+
+hipError_t launch_q_net(const float *img, const NetImage &m, int O, const float *obs, const float *actions,
+                        const float *reward, const float *done, float g, float *out, int64_t rows, hipStream_t stream) {
+    const size_t lds = net_lds_bytes(m);
+    const bool target = reward != nullptr;
+    // what critic_spec_check and the entry points refuse
+    if (rows < 1 || O < 1 || O >= m.O || lds > kNetMaxLds || m.N3 != kNetTile || critic_blocks(rows) > kCriticMaxBlocks ||
+        !img || !obs || !actions || !out || (target && !done))
+        return hipErrorInvalidValue;
+    if (lds > 64u * 1024u && critic_kernels_init() != hipSuccess) return critic_kernels_init();
+    const dim3 grid((unsigned)critic_blocks(rows)), block(kNetBlock);
+    auto kern = m.activation == POLICY_RELU ? (target ? q_net_kernel<false, true> : q_net_kernel<false, false>)
+                                            : (target ? q_net_kernel<true, true> : q_net_kernel<true, false>);
+    return launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, img, m, obs, actions, O, reward, done, g, out,
+                         rows);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sng_ddpg_host.h"
 #include "sng_layout.h"
 #include "sng_noise_host.h"
 #include "sng_policy_host.h"
@@ -93,6 +94,19 @@ hipError_t ppo_net_kernels_init();
 // noise_pack_params fills.
 hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint64_t *counter, int64_t env_offset,
                              float *out, int32_t days, int T, int64_t E, hipStream_t stream);
+// A replay ring's push (sng_ddpg.h, replay_push_kernel): the segments replay_push_args lists, in one launch.
+hipError_t launch_replay_push(const PushArgs &a, hipStream_t stream);
+// A ring's sample (replay_sample_kernel): `batch` rows of the n transitions of days of T steps of E envs, with the
+// sample's key (replay_sample_key).
+hipError_t launch_replay_sample(const ReplayStorage &ring, const SngReplayBatch &out, uint32_t key, uint64_t n, int T,
+                                int64_t E, int O, int A, int64_t batch, hipStream_t stream);
+// Q over `rows` rows (q_net_kernel): img is the critic's device image `m` describes (m.O = O + the action width); with
+// reward and done the TD targets with g = (float)gamma instead.  hipErrorInvalidValue for what critic_spec_check and the
+// entry points refuse.
+hipError_t launch_q_net(const float *img, const NetImage &m, int O, const float *obs, const float *actions,
+                        const float *reward, const float *done, float g, float *out, int64_t rows, hipStream_t stream);
+// q_net_kernel's dynamic-LDS limit, raised once; called by sng_critic_create so that no capture is the first to ask.
+hipError_t critic_kernels_init();
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

@@ -119,10 +119,13 @@ struct NetTrunk {
 // has one tile (the value net's), known at compile time.  That flag, the image's description by value, the row tile
 // as its first row and the lane left to the kernels are what make both kernels compile to the code they had with the
 // trunk written out in each, but for the sense of a branch behind the layers; other spellings of this interface cost
-// either kernel about half a percent (profiles/mlp_refactor_ab.txt).
-template <bool TANH, bool ONE_TILE = false>
+// either kernel about half a percent (profiles/mlp_refactor_ab.txt).  TWO_SRC (q_net_kernel, sng_ddpg.h): a row is
+// obs[row][0 .. O1) followed by src2[row][0 .. m.O - O1), the staging loop's sibling below; the kernels without it
+// compile to the code they had before it existed (profiles/ddpg_codeobj_diff.txt).
+template <bool TANH, bool ONE_TILE = false, bool TWO_SRC = false>
 __device__ __forceinline__ NetTrunk net_trunk(const float *__restrict__ img, const NetImage m,
-                                              const float *__restrict__ obs, int64_t E) {
+                                              const float *__restrict__ obs, int64_t E,
+                                              const float *__restrict__ src2 = nullptr, int O1 = 0) {
     extern __shared__ float4 policy_net_lds4[];
     float *s_h1 = reinterpret_cast<float *>(policy_net_lds4);
     const int h1s = net_lds_h1_stride(m.N1), xs = net_lds_obs_stride(m.K1), cs = net_lds_chunk_stride();
@@ -133,9 +136,20 @@ __device__ __forceinline__ NetTrunk net_trunk(const float *__restrict__ img, con
     const int64_t e0 = (int64_t)blockIdx.x * kNetRows;
     const int rows = E - e0 < kNetRows ? (int)(E - e0) : kNetRows;
     // the observation rows; zeros past O (the chains' trailing terms) and in the rows without an env
-    for (int i = tid; i < kNetRows * m.K1; i += kNetBlock) {
-        const int r = i / m.K1, c = i - r * m.K1;
-        s_x[r * xs + c] = (r < rows && c < m.O) ? obs[(size_t)(e0 + r) * (size_t)m.O + (size_t)c] : 0.f;
+    if constexpr (TWO_SRC) {
+        const int O2 = m.O - O1;
+        for (int i = tid; i < kNetRows * m.K1; i += kNetBlock) {
+            const int r = i / m.K1, c = i - r * m.K1;
+            float v = 0.f;
+            if (r < rows && c < O1) v = obs[(size_t)(e0 + r) * (size_t)O1 + (size_t)c];
+            else if (r < rows && c < m.O) v = src2[(size_t)(e0 + r) * (size_t)O2 + (size_t)(c - O1)];
+            s_x[r * xs + c] = v;
+        }
+    } else {
+        for (int i = tid; i < kNetRows * m.K1; i += kNetBlock) {
+            const int r = i / m.K1, c = i - r * m.K1;
+            s_x[r * xs + c] = (r < rows && c < m.O) ? obs[(size_t)(e0 + r) * (size_t)m.O + (size_t)c] : 0.f;
+        }
     }
     __syncthreads();
     const int arow = rt * kNetTile + (lane & 31), ak = lane >> 5;

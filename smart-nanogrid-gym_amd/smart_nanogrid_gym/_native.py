@@ -144,6 +144,19 @@ class SngNoiseSpec(ctypes.Structure):
                 ("theta", ctypes.c_double), ("dt", ctypes.c_double)]
 
 
+class SngReplaySpec(ctypes.Structure):
+    _fields_ = [("capacity_days", ctypes.c_int32), ("seed", ctypes.c_uint64), ("obs", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p)]
+
+
+class SngReplayBatch(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in ("obs", "actions", "next_obs", "reward", "done", "index")]
+
+
+class SngCriticSpec(ctypes.Structure):
+    _fields_ = [("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32), ("activation", ctypes.c_int32)]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -225,6 +238,33 @@ EXPORTS = {
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.POINTER(SngInfo), ctypes.c_int, ctypes.c_int32,
                                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_replay_create": (ctypes.c_int, [_H, ctypes.POINTER(SngReplaySpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_replay_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, _S]),
+    "sng_replay_size": (ctypes.c_int64, [ctypes.c_void_p]),
+    "sng_replay_state": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, c_int32_p]),
+    "sng_replay_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(SngReplayBatch), _S]),
+    "sng_replay_get_counter": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "sng_replay_set_counter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "sng_replay_destroy": (None, [ctypes.c_void_p]),
+    "sng_replay_host_indices": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "sng_critic_create": (ctypes.c_int, [_H, ctypes.POINTER(SngCriticSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_critic_set_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngMlpWeights), _S]),
+    "sng_critic_q": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, _S]),
+    "sng_critic_targets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                          ctypes.c_void_p, _S]),
+    "sng_critic_destroy": (None, [ctypes.c_void_p]),
+    "sng_critic_host_q": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SngCriticSpec),
+                                         ctypes.POINTER(SngMlpWeights), ctypes.c_int64, c_float_p, c_float_p, c_float_p]),
+    "sng_critic_host_targets": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SngCriticSpec),
+                                               ctypes.POINTER(SngMlpWeights), ctypes.POINTER(SngMlpNetSpec),
+                                               ctypes.POINTER(SngMlpWeights), ctypes.c_int64, c_float_p, c_float_p,
+                                               c_float_p, ctypes.c_double, c_float_p, ctypes.c_int, c_float_p]),
+    "sng_policy_actions_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, _S]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

@@ -119,6 +119,16 @@ def actor_weights(weights, obs_dim, act_dim, net_arch=(HIDDEN, HIDDEN)):
     return arrs
 
 
+def prefixed_weights(state_dict, prefix, what="weights"):
+    """The six entries `prefix`.{0,2,4}.{weight,bias} of a state_dict, in actor_weights' order: a three-layer
+    nn.Sequential as SB3's TD3Policy names its nets (actor.mu, actor_target.mu, critic.qf0, critic_target.qf0)."""
+    keys = [f"{prefix}.{layer}.{part}" for layer in (0, 2, 4) for part in ("weight", "bias")]
+    missing = [k for k in keys if k not in state_dict]
+    if missing:
+        raise KeyError(f"{what}: missing {missing}")
+    return [state_dict[k] for k in keys]
+
+
 def _spec(obs_dim, act_dim, activation, low, high, hidden=HIDDEN):
     spec = _native.SngMlpSpec(obs_dim, act_dim, hidden, ACTIVATIONS[activation], None, None)
     if low is not None:
@@ -234,9 +244,13 @@ class MlpActor(_Handle):
         """SB3's DDPG("MlpPolicy", env) actor: 400-300, relu, squashed into venv.action_space."""
         return cls(venv, activation="relu", net_arch=DDPG_NET_ARCH, squash=True)
 
-    def load(self, weights):
+    def load(self, weights, prefix=None):
         """Upload weights: six arrays or tensors (w1, b1, w2, b2, w3, b3 in torch's [out, in] layout) or a dict with
-        SB3's actor keys (PPO's or DDPG's).  Graphs captured with this actor use them from their next launch on."""
+        SB3's actor keys (PPO's or DDPG's).  prefix: with a dict, the net's entries `prefix`.{0,2,4}.{weight,bias}
+        instead, e.g. "actor_target.mu" for DDPG's target actor.  Graphs captured with this actor use them from their
+        next launch on."""
+        if prefix is not None and isinstance(weights, dict):
+            weights = prefixed_weights(weights, prefix, "actor weights")
         arrs = actor_weights(weights, self.obs_dim, self.act_dim, self.net_arch)
         w = _weights_struct(arrs)
         with torch.cuda.device(self.venv.device):

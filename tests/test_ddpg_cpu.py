@@ -1,0 +1,230 @@
+"""The off-policy side of DDPG (sng_replay_*, sng_critic_*; smart_nanogrid_gym/ddpg.py), without a GPU: the host models
+of csrc/sng_ddpg_host.h against naive evaluations (a stand-alone g++ program, bitwise; once more under the host
+sanitizers: the ring's bookkeeping at capacity 3 with pushes of 2, 2, 1 and 3 days is checked there, in a pure-host
+mirror of the storage), the sampling law's range, determinism and uniformity, host Q against a float64 numpy MLP on
+concatenated rows, host targets against the formula in numpy float32, and every refusal through the host entry points."""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from policy_net_cases import net_f32_rounding_bound, net_f64, random_net_weights
+from smart_nanogrid_gym import _native, ddpg, policy
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "smart-nanogrid-gym_amd", "csrc")
+INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
+SOURCE = os.path.join(ROOT, "tests", "native", "ddpg_host_check.cpp")
+NETS = [(8, 8), (33, 65), (400, 300), (512, 512)]
+P_MIN = 1e-4   # tests/test_gpu_generator_distributions.py's bound for its chi-square tests
+
+needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+err = lambda: _native.lib().sng_last_error(None)   # noqa: E731
+
+
+def _run_native(tmp_path, name, extra):
+    exe = str(tmp_path / name)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *extra, *INCLUDES, SOURCE, "-o", exe],
+                   check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "ddpg host ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    assert int(out.stdout.split()[-2]) > 10000
+
+
+@needs_gxx
+def test_host_models_equal_naive_evaluations_bitwise(tmp_path):
+    _run_native(tmp_path, "ddpg_host_check", ["-O2"])
+
+
+@needs_gxx
+def test_host_models_under_the_host_sanitizers(tmp_path):
+    """The same stand-alone program with -fsanitize=address,undefined, run directly."""
+    _run_native(tmp_path, "ddpg_host_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+# ------------------------------------------------------------------------------------------------------ sampling law
+@pytest.mark.parametrize("n", [1, 2, 5040, 2 ** 31 + 7, 2 ** 40 + 1])
+def test_every_index_is_below_n(n):
+    for seed, off, counter in ((0, 0, 0), (7, 65536, 3), (2 ** 63 + 5, 2 ** 33 + 1, 2 ** 32 + 9)):
+        idx = ddpg.replay_host_indices(seed, off, counter, n, 4096)
+        assert idx.dtype == np.int64 and idx.min() >= 0 and idx.max() < n
+        if n > 2:   # the whole range is reached, above 2^32 too
+            assert idx.max() > n // 2 > idx.min()
+        if n == 1:
+            assert not idx.any()
+
+
+def test_counters_seeds_and_offsets_give_their_own_batches():
+    base = ddpg.replay_host_indices(5, 0, 0, 5040, 256)
+    assert np.array_equal(base, ddpg.replay_host_indices(5, 0, 0, 5040, 256))
+    assert np.array_equal(base[:64], ddpg.replay_host_indices(5, 0, 0, 5040, 64))   # a row depends on its own b only
+    for other in ((5, 0, 1), (5, 0, 2 ** 32), (6, 0, 0), (5 + 2 ** 32, 0, 0), (5, 70, 0), (5, 2 ** 32, 0)):
+        got = ddpg.replay_host_indices(*other, 5040, 256)
+        assert (got != base).mean() > 0.9, other
+
+
+def test_chi_square_of_2_to_20_draws_over_three_days():
+    """n = 5040 = 3 days x 24 steps x 70 envs.  The draw is deterministic: p = 0.37 for this seed."""
+    stats = pytest.importorskip("scipy.stats")
+    n = 3 * 24 * 70
+    idx = ddpg.replay_host_indices(1234, 0, 0, n, 2 ** 20)
+    counts = np.bincount(idx, minlength=n)
+    assert counts.size == n
+    p = stats.chisquare(counts).pvalue
+    print(f"chi-square p = {p:.4f}")
+    assert p > P_MIN
+
+
+def test_no_index_lands_in_an_unfilled_slot():
+    """filled = 2 of capacity 3: slot = i // (T E) stays below filled, in physical slot order."""
+    T, E, filled = 24, 70, 2
+    idx = ddpg.replay_host_indices(9, 0, 4, filled * T * E, 2 ** 16)
+    slot, t, e = idx // (T * E), (idx // E) % T, idx % E
+    assert set(np.unique(slot)) == {0, 1} and set(np.unique(t)) == set(range(T)) and set(np.unique(e)) == set(range(E))
+
+
+def test_sampling_refusals():
+    out = np.zeros(4, np.int64)
+    P = out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    L = _native.lib()
+    assert L.sng_replay_host_indices(0, 0, 0, 0, 4, P) == -1 and b"empty" in err()
+    assert L.sng_replay_host_indices(0, 0, 0, 10, 0, P) == -1 and b"batch" in err()
+    assert L.sng_replay_host_indices(0, 0, 0, 10, 4, None) == -1
+    assert L.sng_replay_host_indices(0, 0, 0, 10, 4, P) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------- host Q
+def rows(obs_dim, act_dim, seed, n=41):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(0, 1, (n, obs_dim)).astype(np.float32), rng.uniform(-1, 1, (n, act_dim)).astype(np.float32))
+
+
+@pytest.mark.parametrize("activation", ["relu", "tanh"])
+@pytest.mark.parametrize("net_arch", NETS, ids=lambda a: f"{a[0]}-{a[1]}")
+def test_host_q_against_float64_on_concatenated_rows(net_arch, activation):
+    """The rule of tests/test_policy_net_cpu.py for mlp_net_host: within net_f32_rounding_bound of the float64 MLP."""
+    O, A = 29, 11
+    obs, actions = rows(O, A, net_arch[0])
+    weights = random_net_weights(O + A, 1, net_arch, seed=3, out_scale=30.0)
+    q = ddpg.host_q(obs, actions, weights, net_arch, activation)
+    x = np.concatenate([obs, actions], axis=1)
+    ref = net_f64(x, weights, activation)[:, 0]
+    bound = net_f32_rounding_bound(x, weights, activation)[:, 0]
+    error = np.abs(q.astype(np.float64) - ref)
+    print(f"{net_arch} {activation}: max err {error.max():.3e}, bound there {bound[error.argmax()]:.3e}")
+    assert (error <= bound).all() and np.unique(q).size > q.size // 2
+    # ... and it is the net actor's host model with one action on those rows
+    want, _ = policy.host_actions(x, weights, activation, net_arch=net_arch, net=True)
+    assert q.tobytes() == want[:, 0].tobytes()
+    # the action columns are read: other actions, another Q
+    assert (ddpg.host_q(obs, -actions, weights, net_arch, activation) != q).mean() > 0.9
+
+
+# ------------------------------------------------------------------------------------------------------ host targets
+@pytest.mark.parametrize("gamma", [0.99, 0.9, 0.0, 1.0])
+def test_host_targets_are_the_formula_in_float32_bitwise(gamma):
+    O, A, arch = 29, 11, (33, 65)
+    rng = np.random.default_rng(8)
+    nobs, na = rows(O, A, 2)
+    n = nobs.shape[0]
+    reward = (-40.0 * rng.random(n)).astype(np.float32)
+    done = (np.arange(n) % 3 == 0).astype(np.float32)
+    assert set(np.unique(done)) == {0.0, 1.0}
+    weights = random_net_weights(O + A, 1, arch, seed=3, out_scale=30.0)
+    y, na_out = ddpg.host_targets(nobs, reward, done, weights, gamma, arch, next_actions=na)
+    assert na_out.tobytes() == na.tobytes()
+    q = ddpg.host_q(nobs, na, weights, arch)
+    nn = np.float32(1.0) - done
+    want = reward + ((nn * np.float32(gamma)) * q)
+    assert want.dtype == np.float32 and y.tobytes() == want.tobytes()
+    if gamma:
+        assert (y[done == 0] != reward[done == 0]).all()
+    assert np.array_equal(y[done == 1], reward[done == 1])
+    # with the target actor's host model in front: a' is sng_policy_net_host_actions' stored action
+    low, high = np.zeros(A, np.float32), np.ones(A, np.float32)
+    aw = random_net_weights(O, A, (16, 24), seed=5, out_scale=4.0)
+    actor = dict(weights=aw, net_arch=(16, 24), activation="relu", squash=True, low=low, high=high)
+    y2, na2 = ddpg.host_targets(nobs, reward, done, weights, gamma, arch, actor=actor)
+    a_want, _ = policy.host_actions(nobs, aw, "relu", low, high, net_arch=(16, 24), squash=True)
+    assert na2.tobytes() == a_want.tobytes() and (np.abs(na2) <= 1).all()
+    assert y2.tobytes() == ddpg.host_targets(nobs, reward, done, weights, gamma, arch, next_actions=na2)[0].tobytes()
+
+
+# --------------------------------------------------------------------------------------------------------- refusals
+def _q_rc(net=(33, 65), O=11, A=3, activation=1, weights="good", spec=True):
+    F = _native.c_float_p
+    if weights == "good":
+        weights = random_net_weights(O + A, 1, net, seed=1)
+    w = None if weights is None else ctypes.byref(_native.SngMlpWeights(*[x.ctypes.data_as(F) for x in weights]))
+    s = ctypes.byref(_native.SngCriticSpec(net[0], net[1], activation)) if spec else None
+    obs, act, out = np.zeros((2, max(O, 1)), np.float32), np.zeros((2, max(A, 1)), np.float32), np.zeros(2, np.float32)
+    return _native.lib().sng_critic_host_q(O, A, s, w, 2, obs.ctypes.data_as(F), act.ctypes.data_as(F), out.ctypes.data_as(F))
+
+
+def test_critic_refusals_through_the_host_entry_point():
+    assert _q_rc() == 0
+    for net in ((7, 64), (64, 7), (513, 64), (64, 513)):
+        assert _q_rc(net=net, weights=None) == -2 and b"8 .. 512" in err(), net
+    # 50 chargers: the input width is 109 + 51 = 160.  400-300 fits, 512-512 does not, and says so with the byte counts
+    zero = [np.zeros(s, np.float32) for s in ((400, 160), (400,), (300, 400), (300,), (1, 300), (1,))]
+    assert _q_rc(net=(400, 300), O=109, A=51, weights=zero) == 0
+    assert _q_rc(net=(512, 512), O=109, A=51, weights=None) == -2
+    assert all(x in err() for x in (b"109 + 51", b"obs_dim 160", b"512-512", b"172544", b"163840")), err()
+    assert _q_rc(spec=False) == -1 and b"null" in err()
+    assert _q_rc(activation=2) == -1 and _q_rc(O=0) == -1 and _q_rc(A=0) == -1
+    assert _q_rc(weights=None) == -1 and b"null critic weights" in err()
+    good = random_net_weights(14, 1, (33, 65), seed=1)
+    for part, bad in ((0, np.nan), (1, np.inf), (2, -np.inf), (4, np.nan), (5, np.inf)):
+        w = [x.copy() for x in good]
+        w[part].flat[w[part].size - 1] = bad
+        assert _q_rc(weights=w) == -1 and b"non-finite critic weight" in err(), (part, bad)
+
+
+def test_target_refusals_through_the_host_entry_point():
+    O, A, arch = 11, 3, (33, 65)
+    weights = random_net_weights(O + A, 1, arch, seed=1)
+    nobs, na = rows(O, A, 0, n=5)
+    r, d = np.zeros(5, np.float32), np.zeros(5, np.float32)
+    for bad in (1.5, -0.01, np.nan, np.inf):
+        with pytest.raises(_native.NativeError, match="gamma"):
+            ddpg.host_targets(nobs, r, d, weights, bad, arch, next_actions=na)
+    for fine in (0.0, 1.0):
+        ddpg.host_targets(nobs, r, d, weights, fine, arch, next_actions=na)
+    with pytest.raises(ValueError, match="next_actions or the target actor"):
+        ddpg.host_targets(nobs, r, d, weights, 0.99, arch)
+    with pytest.raises(ValueError, match="rewards and dones"):
+        ddpg.host_targets(nobs, r[:4], d, weights, 0.99, arch, next_actions=na)
+    # no target actor where the actions are to be computed
+    F = _native.c_float_p
+    s = _native.SngCriticSpec(arch[0], arch[1], 1)
+    w = _native.SngMlpWeights(*[x.ctypes.data_as(F) for x in weights])
+    y = np.zeros(5, np.float32)
+    args = (nobs.ctypes.data_as(F), r.ctypes.data_as(F), d.ctypes.data_as(F), 0.99, na.ctypes.data_as(F))
+    L = _native.lib()
+    assert L.sng_critic_host_targets(O, A, ctypes.byref(s), ctypes.byref(w), None, None, 5, *args, 0, y.ctypes.data_as(F)) == -1
+    assert b"target actor" in err()
+    assert L.sng_critic_host_targets(O, A, ctypes.byref(s), ctypes.byref(w), None, None, 5, *args, 1, y.ctypes.data_as(F)) == 0
+    assert L.sng_critic_host_targets(O, A, ctypes.byref(s), ctypes.byref(w), None, None, 0, *args, 1, y.ctypes.data_as(F)) == -1
+    assert L.sng_critic_host_targets(O, A, ctypes.byref(s), ctypes.byref(w), None, None, 5, *args, 1, None) == -1
+
+
+def test_state_dict_loading_takes_td3s_keys():
+    O, A, arch = 11, 3, (33, 65)
+    critic, target = random_net_weights(O + A, 1, arch, seed=6), random_net_weights(O + A, 1, arch, seed=7)
+    names = [f"{layer}.{part}" for layer in (0, 2, 4) for part in ("weight", "bias")]
+    sd = {f"critic.qf0.{k}": v for k, v in zip(names, critic)}
+    sd.update({f"critic_target.qf0.{k}": v for k, v in zip(names, target)})
+    sd.update({f"actor_target.mu.{k}": v for k, v in zip(names, random_net_weights(O, A, arch, seed=8))})
+    assert all(np.array_equal(a, b) for a, b in zip(ddpg.critic_weights(sd, O, A, arch), critic))
+    assert all(np.array_equal(a, b) for a, b in zip(ddpg.critic_weights(sd, O, A, arch, "critic_target.qf0"), target))
+    assert all(np.array_equal(a, b) for a, b in zip(ddpg.critic_weights(critic, O, A, arch), critic))
+    assert [a.shape for a in policy.prefixed_weights(sd, "actor_target.mu")] == [(33, 11), (33,), (65, 33), (65,), (3, 65), (3,)]
+    with pytest.raises(KeyError, match=r"critic\.qf1\.0\.weight"):
+        ddpg.critic_weights(sd, O, A, arch, "critic.qf1")
+    with pytest.raises(ValueError, match="shapes"):
+        ddpg.critic_weights(sd, O, A + 1, arch)
+    obs, actions = rows(O, A, 1)
+    assert ddpg.host_q(obs, actions, sd, arch).tobytes() == ddpg.host_q(obs, actions, critic, arch).tobytes()
