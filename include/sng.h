@@ -659,7 +659,7 @@ int sng_graph_create_policy_noise(SngEnv *env, SngPolicy *policy, SngNoise *nois
  * The off-policy side of DDPG / TD3 (solvers/RL/ddpg_train.py): a replay ring of whole days, its sampler, the critic
  * Q(s, a) and the TD targets -- everything between "a closed-loop day ended" and "the caller holds a minibatch and its
  * targets", on the device, each with an exact host model (csrc/sng_ddpg_host.h).  The gradient step and the polyak
- * update stay the caller's, who uploads the weights they give, as with PPO.
+ * update follow below (sng_learner_create); a caller who keeps them in torch uploads the weights they give, as with PPO.
  *
  * Replay ring.  capacity_days slots, each one day of a policy graph's SNG_GRAPH_TRAJECTORY outputs, in device storage
  * the caller provides at create and keeps alive until destroy (as a graph's outputs are the caller's):
@@ -769,6 +769,108 @@ int sng_critic_host_targets(int32_t obs_dim, int32_t act_dim, const SngCriticSpe
  * by sng_policy_create_net is refused (SNG_ERR_UNSUPPORTED). */
 int sng_policy_actions_rows(SngPolicy *policy, int64_t rows, const float *obs, const float *noise, float *actions,
                             float *env_actions, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DDPG's gradient step: one SB3 TD3.train iteration as DDPG runs it (one critic, policy_delay = 1, no target noise)
+ * on the device -- both nets' forward and backward passes, Adam, the polyak update of both targets and the repacking
+ * of the four handles' device images -- as plain launches on one stream, with no synchronisation and no host weight
+ * traffic.  The host model is csrc/sng_ddpg_learn_host.h, whose header comment lists every expression; the device
+ * (csrc/sng_ddpg_learn.h, on the f32-input MFMA) gives the same values (==, the sign of a zero apart) given the
+ * device's own a_pi = tanhf(mean), which the host model takes as an input.
+ *
+ * The learner owns, as plain row-major float32 device arrays in torch's [out][in] layout: the master weights of the
+ * actor, the critic and their targets (taken from host arrays by sng_learner_set_state), Adam's two moments and the
+ * last update's gradients of actor and critic, and the last update's q, dq, a_pi, q_pi [rows] and two losses.
+ *
+ * sng_learner_update(rows, obs, actions, y):
+ *   1. critic: q = Q(s, a); loss = mean((q - y)^2), dq[b] = (2 (q[b] - y[b])) / (float)rows; backward; Adam on the
+ *      critic's masters; polyak of the target critic; both critics' images repacked.
+ *   2. actor, on the critic as updated: a_pi = tanhf(mean(s)); q_pi = Q(s, a_pi); loss = -mean(q_pi), dq_pi[b] =
+ *      -(1 / (float)rows); backward through the critic's data path to the action columns of its input, through
+ *      1 - a_pi^2, and through the actor; Adam on the actor's masters; polyak of the target actor; both actors' images
+ *      repacked.  The next launch of a graph captured with the actor acts with the new weights.
+ * Forward outputs are the k-ordered fmaf chains from the bias of SngMlpNetSpec; a data gradient dIn[b][i] is the fmaf
+ * chain over the layer's outputs j ascending of dOut[b][j] * W[j][i], from 0, masked by the relu (In[b][i] > 0); a
+ * weight gradient dW[j][i] is the fmaf chain over the rows b ascending of dOut[b][j] * In[b][i], from 0, and db[j] the
+ * same ordered sum of dOut[b][j].  Segment law: the rows are cut into segments of SNG_LEARNER_SEGMENT; each segment is
+ * a chain of its own from 0 and the partials are added in ascending segment order (g = p0; g = g + p1; ...); rows <=
+ * SNG_LEARNER_SEGMENT is one chain.  No float atomics anywhere: nothing depends on scheduling.
+ *
+ * Adam (torch.optim.Adam, no weight decay, no amsgrad) on an element, each float32 operation rounded on its own, the
+ * divisions and the square root correctly rounded.  t = 1, 2, .. is a host integer of the handle; with the doubles of
+ * the spec
+ *     step_size = (float)(lr / (1 - beta1^t)),  bc2_sqrt = (float)sqrt(1 - beta2^t)
+ *     m = (float)beta1 * m + (float)(1 - beta1) * g
+ *     v = (float)beta2 * v + ((float)(1 - beta2) * g) * g
+ *     p = p - step_size * (m / (sqrt(v) / bc2_sqrt + (float)eps))
+ * Polyak: target = (float)(1 - tau) * target + (float)tau * p, on the p just updated.  Losses: the row-ordered float32
+ * sums (s = s + d * d; s = s + q_pi; segments as for the weight gradients) divided by (float)rows, the actor's negated.
+ *
+ * Refusals, the reason in sng_last_error: hidden activations other than relu and an actor that is not
+ * sng_policy_create_net's with SNG_MLP_OUT_SQUASH are SNG_ERR_UNSUPPORTED; nets whose widths or activations differ
+ * from their targets', handles of another env, rows < 1 or rows > SNG_LEARNER_MAX_ROWS, non-finite hyper-parameters,
+ * tau outside [0, 1], lr <= 0, betas outside [0, 1), eps < 0 and NULL pointers are SNG_ERR_INVALID_ARGUMENT.  The four
+ * handles must outlive the learner.  The workspace grows (the old block freed and a new one allocated, which
+ * synchronises) only when an update has more rows than every update before it; the pointers sng_learner_last gave
+ * before are then invalid, and if that allocation fails sng_learner_last refuses (SNG_ERR_STATE) until an update
+ * succeeds.  Losses: the sums follow the segment law too.  While a learner lives, its masters are the weights:
+ * sng_policy_set_weights / sng_critic_set_weights on one of its four handles changes that handle's image only until
+ * the next update overwrites it (load the learner with sng_learner_set_state instead).  An update that fails at a
+ * launch (SNG_ERR_HIP) returns at once: launches before it are queued, the critic may have been stepped without the
+ * actor, and the step count is not advanced; restore a known state with sng_learner_set_state. */
+#define SNG_LEARNER_SEGMENT 1024     /* rows of one chain of a weight gradient */
+#define SNG_LEARNER_MAX_ROWS 65536
+typedef struct SngLearnerSpec {
+    double actor_lr, critic_lr;     /* > 0 */
+    double tau;                     /* [0, 1] */
+    double beta1, beta2, eps;       /* Adam's */
+} SngLearnerSpec;
+typedef struct SngNetArrays {       /* a net's six arrays: w1 [h1][in], b1, w2 [h2][h1], b2, w3 [out][h2], b3 */
+    float *w1, *b1, *w2, *b2, *w3, *b3;
+} SngNetArrays;
+enum {                              /* sng_learner_arrays' `which` */
+    SNG_LEARNER_ACTOR = 0, SNG_LEARNER_CRITIC = 1, SNG_LEARNER_ACTOR_TARGET = 2, SNG_LEARNER_CRITIC_TARGET = 3,
+    SNG_LEARNER_ACTOR_M = 4, SNG_LEARNER_ACTOR_V = 5, SNG_LEARNER_CRITIC_M = 6, SNG_LEARNER_CRITIC_V = 7,
+    SNG_LEARNER_ACTOR_GRAD = 8, SNG_LEARNER_CRITIC_GRAD = 9, SNG_LEARNER_ARRAYS = 10
+};
+typedef struct SngLearnerState {    /* host arrays: the masters, the targets, Adam's moments and the step count */
+    SngNetArrays actor, critic, actor_target, critic_target;
+    SngNetArrays actor_m, actor_v, critic_m, critic_v;
+    int64_t step;
+} SngLearnerState;
+typedef struct SngLearnerLast {     /* the last update's outputs: device pointers (sng_learner_last) */
+    int64_t rows;
+    float *q, *dq, *a_pi, *q_pi;    /* [rows], [rows], [rows][act_dim], [rows] */
+    float *critic_loss, *actor_loss;    /* one float each */
+} SngLearnerLast;
+typedef struct SngLearnerTrace {    /* sng_learner_host_update's outputs: host arrays, each may be NULL */
+    float *q, *dq, *q_pi;           /* [rows] */
+    SngNetArrays critic_grad, actor_grad;
+    float *critic_loss, *actor_loss;
+} SngLearnerTrace;
+typedef struct SngLearner SngLearner;
+/* A learner over four handles of `env`; the masters, targets and moments are zero and the step count 0 until
+ * sng_learner_set_state. */
+int sng_learner_create(SngEnv *env, SngPolicy *actor, SngPolicy *actor_target, SngCritic *critic,
+                       SngCritic *critic_target, const SngLearnerSpec *spec, SngLearner **out);
+/* One update on obs [rows][obs_dim], actions [rows][act_dim] and y [rows] (device pointers), asynchronous on `stream`. */
+int sng_learner_update(SngLearner *learner, int64_t rows, const float *obs, const float *actions, const float *y,
+                       void *stream);
+/* The device arrays of one of the ten nets' worth of arrays above; they live as long as the learner. */
+int sng_learner_arrays(SngLearner *learner, int which, SngNetArrays *out);
+/* The last update's outputs; the pointers change when the workspace grows. */
+int sng_learner_last(SngLearner *learner, SngLearnerLast *out);
+int sng_learner_get_step(const SngLearner *learner, int64_t *out);
+/* Masters, targets, moments and the step count from / to host arrays.  set_state also repacks the four handles' device
+ * images from the new masters.  Both synchronise `stream`. */
+int sng_learner_set_state(SngLearner *learner, const SngLearnerState *state, void *stream);
+int sng_learner_get_state(SngLearner *learner, const SngLearnerState *state_out, int64_t *step_out, void *stream);
+void sng_learner_destroy(SngLearner *learner);
+/* Host only: the host model of one update on host arrays; `state` is updated in place, a_pi [rows][act_dim] is read
+ * (the device's, or any stand-in for tanh(mean)).  Validates as the device calls do. */
+int sng_learner_host_update(const SngMlpNetSpec *actor_spec, const SngCriticSpec *critic_spec,
+                            const SngLearnerSpec *spec, SngLearnerState *state, int64_t rows, const float *obs,
+                            const float *actions, const float *y, const float *a_pi, const SngLearnerTrace *trace);
 
 /* Host-only entry points (no GPU needed): the reference-RNG scenario generator, for
  * checking against numpy/Python streams on CPU.  Outputs in SngScenario layout for

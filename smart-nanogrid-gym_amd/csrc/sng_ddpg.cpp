@@ -17,15 +17,6 @@ struct SngReplay {
     uint64_t counter = 0;
 };
 
-// A critic of a handle's envs: its spec, the NetImage of (obs_dim + act_dim, 1, hidden1, hidden2) and the device image
-// q_net_kernel reads, which sng_critic_set_weights packs and uploads.
-struct SngCritic {
-    SngEnv *env = nullptr;
-    SngCriticSpec spec{};
-    NetImage image{};
-    UploadedImage img;
-};
-
 static ReplayStorage storage_of(const SngReplaySpec &s) {
     ReplayStorage r;
     r.obs = s.obs, r.actions = s.actions, r.reward = s.reward, r.done = s.done;

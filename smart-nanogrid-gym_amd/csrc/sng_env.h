@@ -136,6 +136,16 @@ struct SngPolicy {
     float *d_env_actions = nullptr;           // [E][act_dim]
 };
 
+// A critic of a handle's envs (sng_ddpg.cpp): its spec, the NetImage of (obs_dim + act_dim, 1, hidden1, hidden2) and
+// the device image q_net_kernel reads, which sng_critic_set_weights packs and uploads and a learner
+// (sng_ddpg_learn.cpp) rewrites on the device.
+struct SngCritic {
+    SngEnv *env = nullptr;
+    SngCriticSpec spec{};
+    sng::NetImage image{};
+    UploadedImage img;
+};
+
 // An action-noise source of a handle's envs (sng_noise.cpp): the spec, the per-action parameters' device image
 // (sng_noise_host.h, noise_pack_params: mu [A], sd [A]), and the counter of the next block, on the device, which only
 // the kernel behind a fill advances.

@@ -46,6 +46,7 @@
 #include "sng_ppo_net.h"        // value_net_kernel, gae_scan_kernel
 #include "sng_noise.h"          // action_noise_kernel
 #include "sng_ddpg.h"           // replay_push_kernel, replay_sample_kernel, q_net_kernel
+#include "sng_ddpg_learn.h"     // learn_concat_kernel, learn_gemm_kernel, learn_loss_kernel, learn_step_kernel
 
 namespace sng {
 
@@ -674,6 +675,57 @@ hipError_t launch_q_net(const float *img, const NetImage &m, int O, const float 
                                             : (target ? q_net_kernel<true, true> : q_net_kernel<true, false>);
     return launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, img, m, obs, actions, O, reward, done, g, out,
                          rows);
+}
+
+// x = [obs | actions] over `rows` rows (learn_concat_kernel)
+hipError_t launch_learn_concat(const float *obs, const float *actions, float *x, int64_t rows, int O, int A,
+                               hipStream_t stream) {
+    if (rows < 1 || rows > kLearnMaxRows || O < 1 || A < 1 || !obs || !actions || !x) return hipErrorInvalidValue;
+    const int64_t n = rows * ((int64_t)O + A);
+    int64_t blocks = (n + kLearnBlock - 1) / kLearnBlock;
+    blocks = blocks > (1 << 16) ? (1 << 16) : blocks;
+    return launch_kernel(learn_concat_kernel, dim3((unsigned)blocks), dim3(kLearnBlock), 0, stream, nullptr, nullptr, obs,
+                         actions, x, rows, O, A);
+}
+
+// One product of an update (learn_gemm_kernel): grid x over C's column tiles, y over groups of four row tiles, z over
+// the segments of the reduction.
+hipError_t launch_learn_gemm(const LearnGemm &g, int epilogue, hipStream_t stream) {
+    if (g.M < 1 || g.N < 1 || g.K < 1 || g.S < 1 || !g.a || !g.b || !g.c) return hipErrorInvalidValue;
+    if ((epilogue == LEARN_EPI_MASK || epilogue == LEARN_EPI_DTANH) && !g.aux) return hipErrorInvalidValue;
+    if (epilogue == LEARN_EPI_TANH && !g.c2) return hipErrorInvalidValue;
+    const int per = kNetTile * (kLearnBlock / kWave);
+    const int64_t segs = ((int64_t)g.K + g.S - 1) / g.S;
+    const dim3 grid((unsigned)((g.N + kNetTile - 1) / kNetTile), (unsigned)((g.M + per - 1) / per), (unsigned)segs);
+    if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
+    const dim3 block(kLearnBlock);
+    switch (epilogue) {
+    case LEARN_EPI_NONE: return launch_kernel(learn_gemm_kernel<LEARN_EPI_NONE>, grid, block, 0, stream, nullptr, nullptr, g);
+    case LEARN_EPI_RELU: return launch_kernel(learn_gemm_kernel<LEARN_EPI_RELU>, grid, block, 0, stream, nullptr, nullptr, g);
+    case LEARN_EPI_MASK: return launch_kernel(learn_gemm_kernel<LEARN_EPI_MASK>, grid, block, 0, stream, nullptr, nullptr, g);
+    case LEARN_EPI_TANH: return launch_kernel(learn_gemm_kernel<LEARN_EPI_TANH>, grid, block, 0, stream, nullptr, nullptr, g);
+    case LEARN_EPI_DTANH: return launch_kernel(learn_gemm_kernel<LEARN_EPI_DTANH>, grid, block, 0, stream, nullptr, nullptr, g);
+    }
+    return hipErrorInvalidValue;
+}
+
+// dq [rows] and the loss (learn_loss_kernel); y is the critic's, null with `actor`
+hipError_t launch_learn_loss(bool actor, const float *q, const float *y, float *dq, float *loss, int64_t rows,
+                             hipStream_t stream) {
+    if (rows < 1 || rows > kLearnMaxRows || !q || (!actor && !y) || !dq || !loss) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((rows + kLearnBlock - 1) / kLearnBlock + 1)), block(kLearnBlock);
+    return actor ? launch_kernel(learn_loss_kernel<true>, grid, block, 0, stream, nullptr, nullptr, q, y, dq, loss, rows)
+                 : launch_kernel(learn_loss_kernel<false>, grid, block, 0, stream, nullptr, nullptr, q, y, dq, loss, rows);
+}
+
+// A net's Adam step, polyak blend and repack (learn_step_kernel), or with adam = false the repack alone
+hipError_t launch_learn_step(const LearnStep &s, bool adam, hipStream_t stream) {
+    if (s.total < 1 || s.nseg < 1 || !s.img || !s.img_target) return hipErrorInvalidValue;
+    uint64_t blocks = (s.total + kLearnBlock - 1) / kLearnBlock;
+    blocks = blocks > (1u << 16) ? (1u << 16) : blocks;
+    const dim3 grid((unsigned)blocks), block(kLearnBlock);
+    return adam ? launch_kernel(learn_step_kernel<true>, grid, block, 0, stream, nullptr, nullptr, s)
+                : launch_kernel(learn_step_kernel<false>, grid, block, 0, stream, nullptr, nullptr, s);
 }
 
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream) {

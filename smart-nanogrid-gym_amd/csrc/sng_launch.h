@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sng_ddpg_host.h"
+#include "sng_ddpg_learn_host.h"
 #include "sng_layout.h"
 #include "sng_noise_host.h"
 #include "sng_policy_host.h"
@@ -107,6 +108,15 @@ hipError_t launch_q_net(const float *img, const NetImage &m, int O, const float 
                         const float *reward, const float *done, float g, float *out, int64_t rows, hipStream_t stream);
 // q_net_kernel's dynamic-LDS limit, raised once; called by sng_critic_create so that no capture is the first to ask.
 hipError_t critic_kernels_init();
+// A learner's launches (sng_ddpg_learn.h; the structs are sng_ddpg_learn_host.h's): x = [obs | actions]; one matrix
+// product with its epilogue (a LearnEpilogue); a loss and its gradient over the rows; a net's Adam step, polyak blend
+// and repack, or with adam = false the repack alone.  hipErrorInvalidValue for what sng_learner_update refuses.
+hipError_t launch_learn_concat(const float *obs, const float *actions, float *x, int64_t rows, int O, int A,
+                               hipStream_t stream);
+hipError_t launch_learn_gemm(const LearnGemm &g, int epilogue, hipStream_t stream);
+hipError_t launch_learn_loss(bool actor, const float *q, const float *y, float *dq, float *loss, int64_t rows,
+                             hipStream_t stream);
+hipError_t launch_learn_step(const LearnStep &s, bool adam, hipStream_t stream);
 int step_lanes_supported(int n, int lanes);
 // The name rocprofv3 reports for the step kernel launch_step would dispatch next.
 int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);

@@ -1,6 +1,6 @@
 # The library's sources and its build id, shared by csrc/Makefile and tools/diag/Makefile (tools/diag/variant.sh
 # copies csrc/ whole, so this fragment travels with a variant's sources).
-SNG_SRCS := sng_kernels.hip sng_api.cpp sng_state.cpp sng_graph.cpp sng_policy.cpp sng_ppo.cpp sng_noise.cpp sng_ddpg.cpp sng_comm.cpp
+SNG_SRCS := sng_kernels.hip sng_api.cpp sng_state.cpp sng_graph.cpp sng_policy.cpp sng_ppo.cpp sng_noise.cpp sng_ddpg.cpp sng_ddpg_learn.cpp sng_comm.cpp
 # every header of the directory this fragment lies in, sorted: a new header is in the build id and in make's
 # dependencies without being listed anywhere
 SNG_HDRS := $(sort $(notdir $(wildcard $(dir $(lastword $(MAKEFILE_LIST)))*.h)))

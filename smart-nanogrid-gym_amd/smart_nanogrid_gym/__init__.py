@@ -8,13 +8,13 @@ with the reference's id and max_episode_steps (smart_nanogrid_gym/__init__.py:4-
 from .envs import SmartNanogridEnv
 from .evaluation import (RuleBasedController, evaluate_model_for_single_episode, evaluate_models, generate_days,
                          predict_single_day)
-from .ddpg import DdpgCollector, QCritic, ReplayRing, ReplaySamples
+from .ddpg import DdpgCollector, DdpgLearner, QCritic, ReplayRing, ReplaySamples
 from .policy import ActionNoise, ClosedLoopGraph, MlpActor, PpoHead, PpoRollout
 from .recorder import DayRecorder
 from .settings import EnvSettings, parse_time_interval
 from .vec_env import EpisodeGraph, SmartNanogridVecEnv
 
-__all__ = ["SmartNanogridEnv", "SmartNanogridVecEnv", "EpisodeGraph", "MlpActor", "ActionNoise", "ClosedLoopGraph", "PpoHead", "PpoRollout", "ReplayRing", "ReplaySamples", "QCritic", "DdpgCollector", "EnvSettings", "DayRecorder",
+__all__ = ["SmartNanogridEnv", "SmartNanogridVecEnv", "EpisodeGraph", "MlpActor", "ActionNoise", "ClosedLoopGraph", "PpoHead", "PpoRollout", "ReplayRing", "ReplaySamples", "QCritic", "DdpgCollector", "DdpgLearner", "EnvSettings", "DayRecorder",
            "parse_time_interval", "RuleBasedController", "evaluate_model_for_single_episode", "predict_single_day",
            "evaluate_models", "generate_days"]
 

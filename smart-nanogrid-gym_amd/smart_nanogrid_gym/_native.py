@@ -157,6 +157,36 @@ class SngCriticSpec(ctypes.Structure):
     _fields_ = [("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32), ("activation", ctypes.c_int32)]
 
 
+LEARNER_SEGMENT = 1024     # sng.h SNG_LEARNER_SEGMENT
+LEARNER_MAX_ROWS = 65536   # sng.h SNG_LEARNER_MAX_ROWS
+# sng.h SNG_LEARNER_*: sng_learner_arrays' `which`
+LEARNER_ARRAYS = ("actor", "critic", "actor_target", "critic_target", "actor_m", "actor_v", "critic_m", "critic_v",
+                  "actor_grad", "critic_grad")
+
+
+class SngLearnerSpec(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_double) for f in ("actor_lr", "critic_lr", "tau", "beta1", "beta2", "eps")]
+
+
+class SngNetArrays(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
+class SngLearnerState(ctypes.Structure):
+    _fields_ = [(f, SngNetArrays) for f in LEARNER_ARRAYS[:8]] + [("step", ctypes.c_int64)]
+
+
+class SngLearnerLast(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int64)] + [(f, ctypes.c_void_p) for f in ("q", "dq", "a_pi", "q_pi", "critic_loss",
+                                                                           "actor_loss")]
+
+
+class SngLearnerTrace(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("q_pi", ctypes.c_void_p),
+                ("critic_grad", SngNetArrays), ("actor_grad", SngNetArrays), ("critic_loss", ctypes.c_void_p),
+                ("actor_loss", ctypes.c_void_p)]
+
+
 _H, _S = ctypes.c_void_p, ctypes.c_void_p   # handle, hipStream_t
 EXPORTS = {
     "sng_abi_version": (ctypes.c_int32, []),
@@ -265,6 +295,21 @@ EXPORTS = {
                                                c_float_p, ctypes.c_double, c_float_p, ctypes.c_int, c_float_p]),
     "sng_policy_actions_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, _S]),
+    "sng_learner_create": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(SngLearnerSpec), ctypes.POINTER(ctypes.c_void_p)]),
+    "sng_learner_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, _S]),
+    "sng_learner_arrays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SngNetArrays)]),
+    "sng_learner_last": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngLearnerLast)]),
+    "sng_learner_get_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "sng_learner_set_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngLearnerState), _S]),
+    "sng_learner_get_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SngLearnerState),
+                                             ctypes.POINTER(ctypes.c_int64), _S]),
+    "sng_learner_destroy": (None, [ctypes.c_void_p]),
+    "sng_learner_host_update": (ctypes.c_int, [ctypes.POINTER(SngMlpNetSpec), ctypes.POINTER(SngCriticSpec),
+                                               ctypes.POINTER(SngLearnerSpec), ctypes.POINTER(SngLearnerState),
+                                               ctypes.c_int64, c_float_p, c_float_p, c_float_p, c_float_p,
+                                               ctypes.POINTER(SngLearnerTrace)]),
     "sng_host_generate_scenarios": (ctypes.c_int, [ctypes.POINTER(SngConfig), ctypes.c_int64, ctypes.c_uint64,
                                                    ctypes.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                                    c_int32_p, c_int32_p, ctypes.c_int32, c_double_p]),

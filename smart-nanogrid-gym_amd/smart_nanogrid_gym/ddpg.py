@@ -7,7 +7,9 @@ transitions from them with a counter-based integer law that has an exact host mo
 `QCritic` is SB3's ContinuousCritic with one Q net, Linear(O + A, h1)-act-Linear(h1, h2)-act-Linear(h2, 1) on
 cat([obs, action]), on the f32-input MFMA, and the TD targets y = r + gamma (1 - d) Q'(s', pi'(s')) of a sample from a
 target critic and a target MlpActor.  `DdpgCollector` is a closed-loop graph and the push behind it on one stream.
-The gradient step and the polyak update stay the caller's torch, which load()s the weights they give.
+`DdpgLearner` is the gradient step behind them (sng_learner_create): both nets' backward passes, Adam and the polyak
+update on master weights the learner owns on the device, and the four handles' images rewritten in place, so that no
+weight crosses the host between two collected days; `host_update` is its host model.
 """
 import collections
 import ctypes
@@ -352,6 +354,298 @@ class QCritic(_Handle):
                          high=actor_target.high)
         return host_targets(samples.next_observations, samples.rewards, samples.dones, self.weights, gamma,
                             self.net_arch, self.activation, next_actions, actor)
+
+
+# TD3Policy's four nets as SB3's state_dict names them, in sng.h's SNG_LEARNER_* order
+LEARNER_NETS = {"actor": "actor.mu", "critic": SB3_CRITIC_PREFIX, "actor_target": "actor_target.mu",
+                "critic_target": "critic_target.qf0"}
+LEARNER_SEGMENT = _native.LEARNER_SEGMENT
+LEARNER_MAX_ROWS = _native.LEARNER_MAX_ROWS
+
+
+def net_keys(prefix):
+    """`prefix`.{0,2,4}.{weight,bias}: a three-layer nn.Sequential's state_dict keys, in (w1, b1, w2, b2, w3, b3) order."""
+    return [f"{prefix}.{layer}.{part}" for layer in (0, 2, 4) for part in ("weight", "bias")]
+
+
+def _net_shapes(k, h1, h2, n):
+    return [(h1, k), (h1,), (h2, h1), (h2,), (n, h2), (n,)]
+
+
+def _learner_shapes(obs_dim, act_dim, actor_arch, critic_arch):
+    a, c = _net_shapes(obs_dim, *actor_arch, act_dim), _net_shapes(obs_dim + act_dim, *critic_arch, 1)
+    return {"actor": a, "critic": c, "actor_target": a, "critic_target": c}
+
+
+def _arrays_struct(arrs):
+    return _native.SngNetArrays(*[a.ctypes.data for a in arrs])
+
+
+def _learner_spec(actor_lr, critic_lr, tau, betas, eps):
+    return _native.SngLearnerSpec(float(actor_lr), float(critic_lr), float(tau), float(betas[0]), float(betas[1]),
+                                  float(eps))
+
+
+def learner_host_state(params, obs_dim, act_dim, actor_arch=DDPG_NET_ARCH, critic_arch=DDPG_NET_ARCH, exp_avg=None,
+                       exp_avg_sq=None, step=0):
+    """A learner's state for host_update: dict(params=, exp_avg=, exp_avg_sq=, step=), each a dict of float32 arrays
+    under SB3's names -- params the 24 entries of LEARNER_NETS (from a TD3Policy state_dict; other entries are
+    ignored), the moments the 12 of actor.mu.* and critic.qf0.* (zeros when not given).  The arrays are copies."""
+    shapes = _learner_shapes(obs_dim, act_dim, _net_arch(actor_arch), _net_arch(critic_arch))
+    out = dict(params={}, exp_avg={}, exp_avg_sq={}, step=int(step))
+    for net, prefix in LEARNER_NETS.items():
+        for key, shape in zip(net_keys(prefix), shapes[net]):
+            if key not in params:
+                raise KeyError(f"learner state: missing {key}")
+            arr = _as_f32(params[key]).copy()
+            if arr.shape != shape:
+                raise ValueError(f"learner state: {key} must have shape {shape}, got {arr.shape}")
+            out["params"][key] = arr
+            if net in ("actor", "critic"):
+                for name, given in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+                    out[name][key] = np.zeros(shape, np.float32) if given is None else _as_f32(given[key]).copy()
+    return out
+
+
+def _state_struct(state):
+    """(SngLearnerState over the arrays of a learner_host_state dict, which it reads and writes in place)"""
+    nets = []
+    for net, prefix in LEARNER_NETS.items():
+        nets.append(_arrays_struct([state["params"][k] for k in net_keys(prefix)]))
+    moments = []
+    for net in ("actor", "critic"):
+        for name in ("exp_avg", "exp_avg_sq"):
+            moments.append(_arrays_struct([state[name][k] for k in net_keys(LEARNER_NETS[net])]))
+    return _native.SngLearnerState(*nets, *moments, int(state["step"]))
+
+
+def host_update(state, obs, actions, y, a_pi, low, high, actor_arch=DDPG_NET_ARCH, critic_arch=DDPG_NET_ARCH,
+                actor_lr=1e-3, critic_lr=1e-3, tau=0.005, betas=(0.9, 0.999), eps=1e-8, activation="relu",
+                squash=True):
+    """The host model of one DdpgLearner.update (sng_learner_host_update) on numpy: `state` (learner_host_state) is
+    updated in place; obs [B, obs_dim], actions [B, act_dim], y [B]; a_pi [B, act_dim] stands for tanh(actor(obs)) --
+    the device's own for an exact comparison.  low / high: the action Box of the squashed actor.  Returns a dict with q,
+    dq, q_pi [B], critic_loss, actor_loss and grads (the 12 gradients under SB3's names).  Needs no GPU."""
+    obs, actions, a_pi = _as_f32(obs), _as_f32(actions), _as_f32(a_pi)
+    y = _as_f32(y).reshape(-1)
+    if obs.ndim != 2 or actions.ndim != 2:
+        raise ValueError("obs and actions must be [rows, obs_dim] and [rows, act_dim]")
+    rows, O = obs.shape
+    A = actions.shape[1]
+    if actions.shape[0] != rows or y.shape != (rows,) or a_pi.shape != (rows, A):
+        raise ValueError(f"actions, y and a_pi must hold {rows} rows")
+    actor_arch, critic_arch = _net_arch(actor_arch), _net_arch(critic_arch)
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}")
+    if low is not None:
+        low, high = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float32), (A,))) for x in (low, high))
+    aspec = _net_spec(O, A, activation, low, high, actor_arch, squash)
+    cspec = _native.SngCriticSpec(critic_arch[0], critic_arch[1], ACTIVATIONS[activation])
+    spec = _learner_spec(actor_lr, critic_lr, tau, betas, eps)
+    shapes = _learner_shapes(O, A, actor_arch, critic_arch)
+    grads = {k: np.zeros(s, np.float32) for net in ("actor", "critic")
+             for k, s in zip(net_keys(LEARNER_NETS[net]), shapes[net])}
+    q, dq, q_pi = (np.zeros(max(rows, 1), np.float32) for _ in range(3))
+    losses = np.zeros(2, np.float32)
+    trace = _native.SngLearnerTrace(
+        q.ctypes.data, dq.ctypes.data, q_pi.ctypes.data,
+        _arrays_struct([grads[k] for k in net_keys(LEARNER_NETS["critic"])]),
+        _arrays_struct([grads[k] for k in net_keys(LEARNER_NETS["actor"])]), losses.ctypes.data,
+        losses.ctypes.data + 4)
+    st = _state_struct(state)
+    F = _native.c_float_p
+    check(lib().sng_learner_host_update(ctypes.byref(aspec), ctypes.byref(cspec), ctypes.byref(spec), ctypes.byref(st),
+                                        rows, obs.ctypes.data_as(F), actions.ctypes.data_as(F), y.ctypes.data_as(F),
+                                        a_pi.ctypes.data_as(F), ctypes.byref(trace)))
+    state["step"] = int(st.step)
+    return dict(q=q[:rows], dq=dq[:rows], q_pi=q_pi[:rows], critic_loss=losses[0], actor_loss=losses[1], grads=grads)
+
+
+class _DeviceArray:
+    """A float32 array in device memory the library owns, for torch.as_tensor (the CUDA array interface)."""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f4", data=(int(ptr), False), version=2,
+                                             strides=None)
+
+
+class DdpgLearner(_Handle):
+    """DDPG's gradient step on the device (include/sng.h, sng_learner_create): one SB3 TD3.train iteration with one
+    critic -- the critic's step on mean((Q(s, a) - y)^2), the actor's on -mean(Q(s, pi(s))) with the critic as just
+    updated, Adam on both, the polyak update of both targets -- and the four handles' device images rewritten from the
+    new weights, as plain launches on one stream without synchronisation.  A ClosedLoopGraph captured with `actor` acts
+    with the new weights at its next launch, and critic_target.targets uses the new targets.
+
+    actor, actor_target   -- MlpActors of `venv` with squash=True and relu hidden layers, load()ed
+    critic, critic_target -- QCritics of `venv` with relu, load()ed
+    Their loaded weights are the initial master weights; Adam's moments start at zero.  `params` (24 entries), `grads`
+    (12) and `moments` (12 pairs (exp_avg, exp_avg_sq)) are dicts of device tensors the learner owns, keyed by SB3's
+    names: actor.mu.{0,2,4}.{weight,bias}, critic.qf0.*, actor_target.mu.*, critic_target.qf0.*.  update() leaves the
+    handles' host `weights` stale and sets them to None; pull() brings the weights back.
+
+    The tensors of `params`, `grads` and `moments` are views of memory the library owns, valid until close() (clone()
+    what is to outlive the learner).  While a learner lives its masters are the weights: load() on one of its four nets
+    changes that net's device image only until the next update overwrites it from the masters -- give new weights to
+    the learner with load_state(learner_host_state(state_dict, ...)) instead."""
+    _destroy = "sng_learner_destroy"
+    _closed = "the learner is closed"
+
+    def __init__(self, venv, actor, critic, actor_target, critic_target, actor_lr=1e-3, critic_lr=1e-3, tau=0.005,
+                 gamma=0.99, betas=(0.9, 0.999), eps=1e-8):
+        if venv.closed:
+            raise ValueError("venv is closed")
+        for name, net, kind in (("actor", actor, MlpActor), ("actor_target", actor_target, MlpActor),
+                                ("critic", critic, QCritic), ("critic_target", critic_target, QCritic)):
+            if not isinstance(net, kind):
+                raise ValueError(f"{name} must be a {kind.__name__}")
+            if net.venv is not venv:
+                raise ValueError(f"{name} was made for another env batch")
+            if net._p is None:
+                raise ValueError(f"{name} is closed")
+            if net.weights is None:
+                raise ValueError(f"load() {name}'s weights first: they are the learner's initial master weights")
+        self.venv = venv
+        self.actor, self.critic, self.actor_target, self.critic_target = actor, critic, actor_target, critic_target
+        self.gamma = float(gamma)
+        self.hyper = dict(actor_lr=float(actor_lr), critic_lr=float(critic_lr), tau=float(tau),
+                          betas=(float(betas[0]), float(betas[1])), eps=float(eps))
+        self._p = None
+        spec = _learner_spec(actor_lr, critic_lr, tau, betas, eps)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(venv.device):
+            check(lib().sng_learner_create(venv._h, actor._p, actor_target._p, critic._p, critic_target._p,
+                                           ctypes.byref(spec), ctypes.byref(h)), venv._h)
+        self._own(venv, h)
+        self._shapes = _learner_shapes(venv.obs_dim, venv.act_dim, actor.net_arch, critic.net_arch)
+        params = {}
+        for name, net in (("actor", actor), ("critic", critic), ("actor_target", actor_target),
+                          ("critic_target", critic_target)):
+            params.update(zip(net_keys(LEARNER_NETS[name]), net.weights))
+        self.load_state(learner_host_state(params, venv.obs_dim, venv.act_dim, actor.net_arch, critic.net_arch))
+        dev = {which: self._arrays(which) for which in _native.LEARNER_ARRAYS}
+        self.params, self.grads, self.moments = {}, {}, {}
+        for net, prefix in LEARNER_NETS.items():
+            self.params.update(zip(net_keys(prefix), dev[net]))
+        for net in ("actor", "critic"):
+            keys = net_keys(LEARNER_NETS[net])
+            self.grads.update(zip(keys, dev[net + "_grad"]))
+            self.moments.update(zip(keys, zip(dev[net + "_m"], dev[net + "_v"])))
+
+    def _tensor(self, ptr, shape):
+        with torch.cuda.device(self.venv.device):
+            return torch.as_tensor(_DeviceArray(ptr, shape), device=self.venv.device)
+
+    def _arrays(self, which):
+        """The six device tensors of one of _native.LEARNER_ARRAYS."""
+        a = _native.SngNetArrays()
+        check(lib().sng_learner_arrays(self._p, _native.LEARNER_ARRAYS.index(which), ctypes.byref(a)), self.venv._h)
+        net = which.split("_")[0]
+        return [self._tensor(getattr(a, f), s) for f, s in zip(("w1", "b1", "w2", "b2", "w3", "b3"), self._shapes[net])]
+
+    @property
+    def step(self):
+        """Updates so far: Adam's t of the last one."""
+        self._check_open()
+        t = ctypes.c_int64()
+        check(lib().sng_learner_get_step(self._p, ctypes.byref(t)), self.venv._h)
+        return int(t.value)
+
+    def load_state(self, state):
+        """Masters, targets, moments and step from a learner_host_state dict (sng_learner_set_state); the four
+        handles' device images are rewritten from the masters.  Synchronises."""
+        self._check_open()
+        st = _state_struct(state)
+        dev = self.venv.device
+        with torch.cuda.device(dev):
+            check(lib().sng_learner_set_state(self._p, ctypes.byref(st), _stream_handle(dev)), self.venv._h)
+        return self
+
+    def host_state(self):
+        """The learner's state on the host, as learner_host_state gives it (sng_learner_get_state).  Synchronises."""
+        self._check_open()
+        venv = self.venv
+        state = dict(params={}, exp_avg={}, exp_avg_sq={}, step=0)
+        for net, prefix in LEARNER_NETS.items():
+            for key, shape in zip(net_keys(prefix), self._shapes[net]):
+                state["params"][key] = np.zeros(shape, np.float32)
+                if net in ("actor", "critic"):
+                    state["exp_avg"][key] = np.zeros(shape, np.float32)
+                    state["exp_avg_sq"][key] = np.zeros(shape, np.float32)
+        st = _state_struct(state)
+        t = ctypes.c_int64()
+        with torch.cuda.device(venv.device):
+            check(lib().sng_learner_get_state(self._p, ctypes.byref(st), ctypes.byref(t), _stream_handle(venv.device)),
+                  venv._h)
+        state["step"] = int(t.value)
+        return state
+
+    def pull(self):
+        """The 24 weights as a state_dict of numpy arrays under SB3's names, ready for TD3Policy.load_state_dict after
+        torch.from_numpy; the four handles' `weights` are refreshed from it, so their host_* methods work again."""
+        sd = self.host_state()["params"]
+        for name, net in (("actor", self.actor), ("critic", self.critic), ("actor_target", self.actor_target),
+                          ("critic_target", self.critic_target)):
+            net.weights = [sd[k] for k in net_keys(LEARNER_NETS[name])]
+        return sd
+
+    def update(self, samples, y=None, stream=None):
+        """One update on a ReplaySamples (or anything with observations and actions, and for y=None what
+        QCritic.targets reads).  y [B, 1] or [B]: the TD targets; None: critic_target.targets(actor_target, samples,
+        gamma) is called first.  Launches on torch's current stream (or `stream`), no synchronisation."""
+        self._check_open()
+        for name, net in (("actor", self.actor), ("critic", self.critic), ("actor_target", self.actor_target),
+                          ("critic_target", self.critic_target)):
+            if net._p is None:
+                raise RuntimeError(f"{name} was closed: a DdpgLearner needs its four nets for every update")
+        dev = self.venv.device
+        obs, act = samples.observations, samples.actions
+        rows = int(obs.shape[0]) if obs.dim() == 2 else -1
+        _want(obs, "samples.observations", (rows, self.venv.obs_dim), torch.float32, dev)
+        _want(act, "samples.actions", (rows, self.venv.act_dim), torch.float32, dev)
+        if rows < 1 or rows > LEARNER_MAX_ROWS:
+            raise ValueError(f"an update takes 1 .. {LEARNER_MAX_ROWS} rows, got {rows}")
+        if y is None:
+            y, _ = self.critic_target.targets(self.actor_target, samples, self.gamma, stream)
+        if y.numel() != rows or y.dtype != torch.float32 or y.device != dev or not y.is_contiguous():
+            raise ValueError(f"y must be a contiguous float32 tensor of {rows} values on {dev}")
+        p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        with torch.cuda.device(dev):
+            check(lib().sng_learner_update(self._p, rows, p(obs), p(act), p(y), _stream_arg(dev, stream)), self.venv._h)
+        self._last_y = y
+        for net in (self.actor, self.critic, self.actor_target, self.critic_target):
+            net.weights = None   # stale until pull()
+        return self
+
+    def train(self, ring, batch, gradient_steps=1, stream=None):
+        """SB3's train(gradient_steps, batch_size): sample -> targets -> update, gradient_steps times, on torch's
+        current stream (or `stream`) without synchronising."""
+        if not isinstance(ring, ReplayRing) or ring.venv is not self.venv:
+            raise ValueError("ring must be a ReplayRing of the learner's env batch")
+        for _ in range(int(gradient_steps)):
+            self.update(ring.sample(batch, stream), stream=stream)
+        return self
+
+    @property
+    def last(self):
+        """The last update's q [B], dq [B], y, a_pi [B, act_dim], q_pi [B], critic_loss and actor_loss (0-dim): device
+        tensors the learner owns (y: the caller's or the target critic's), overwritten by the next update.  They are
+        views of the learner's workspace, not copies: an update with more rows than any before it frees and reallocates
+        that workspace, and close() frees it, after which tensors taken earlier must not be used -- take `last` again
+        after such an update, and clone() what is to be kept."""
+        self._check_open()
+        o = _native.SngLearnerLast()
+        check(lib().sng_learner_last(self._p, ctypes.byref(o)), self.venv._h)
+        B, A = int(o.rows), self.venv.act_dim
+        return dict(q=self._tensor(o.q, (B,)), dq=self._tensor(o.dq, (B,)), y=self._last_y,
+                    a_pi=self._tensor(o.a_pi, (B, A)), q_pi=self._tensor(o.q_pi, (B,)),
+                    critic_loss=self._tensor(o.critic_loss, (1,)).reshape(()),
+                    actor_loss=self._tensor(o.actor_loss, (1,)).reshape(()))
+
+    def host_update(self, state, obs, actions, y, a_pi):
+        """The host model of update() with this learner's nets and hyper-parameters (see host_update)."""
+        return host_update(state, obs, actions, y, a_pi, self.actor.low, self.actor.high, self.actor.net_arch,
+                           self.critic.net_arch, activation=self.actor.activation, squash=self.actor.squash,
+                           **self.hyper)
 
 
 class DdpgCollector:
