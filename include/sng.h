@@ -325,7 +325,7 @@ int sng_get_tables(const SngEnv *env, double *irr, double *irr_max, double *pv_p
  * steps-only graph over a day of another encoding than at capture, or after t = 0, fails with
  * SNG_ERR_STATE.
  * A reset graph of two or more days without SNG_GRAPH_TRAJECTORY, at the stations whose day measured shorter that
- * way (csrc/sng_step_plan.h, reset_overlapped: 10 chargers without V2X or stochastic profiles), generates day
+ * way (csrc/sng_graph_form.h, reset_overlapped: 10 chargers without V2X or stochastic profiles), generates day
  * d + 1 while day d is stepped: the generator nodes sit on a parallel branch
  * of the graph and write every other day into a second set of day buffers the handle allocates for this (about
  * the size of one packed day).  The days drawn, the outputs, the day returns and the state the graph leaves --
@@ -356,6 +356,11 @@ int sng_graph_day_kernel_name(const SngGraph *graph, char *buf, int32_t len);
 int sng_graph_step_nodes(const SngGraph *graph);
 /* 1: the graph generates day d + 1 beside day d's steps (above); 0: the serial chain (-1 for NULL). */
 int sng_graph_reset_overlapped(const SngGraph *graph);
+/* The captured graph as text, one line per node in hipGraphGetNodes order: "<index> <type>", for a kernel node its name
+ * (hipKernelNameRefByPtr), "grid=(x,y,z) block=(x,y,z) lds=<dynamic LDS bytes>", and "deps=[...]", the indices of the
+ * nodes it depends on, ascending.  Returns the text's length without its NUL (buf holds the text when that is below
+ * len; else call again with more room), or a negative SNG_ERR_* code.  For tests and A/B tools: what a capture made. */
+int sng_graph_describe(const SngGraph *graph, char *buf, int64_t len);
 /* Kernel-time probe: runs `days` device-RNG days eagerly (as the graph does) and returns the
  * device time (ms) of every step kernel, ms[days*T], from HIP start/stop events attached to
  * each dispatch (hipExtLaunchKernel: the dispatch's own begin/end timestamps), and, when reset_ms
@@ -413,7 +418,7 @@ void sng_policy_destroy(SngPolicy *policy);
  * rules (the loaded day's encoding, t = 0) included; a steps-only graph reads the day's t = 0 observation from obs
  * (block [0][0] with SNG_GRAPH_TRAJECTORY), where the reset or the caller left it.  actions_out receives a: one block
  * [num_envs][act_dim] that every step overwrites, or [days][T][num_envs][act_dim] with SNG_GRAPH_TRAJECTORY.
- * The form of a day is decided per plan in csrc/sng_step_plan.h (policy_day_form).  Node form: T x (policy_kernel
+ * The form of a day is decided per plan in csrc/sng_graph_form.h (policy_day_form).  Node form: T x (policy_kernel
  * node, step node), the step nodes being those of sng_graph_create; sng_graph_step_nodes reports 2T.  Fused form: one
  * node a day, day_lean_policy_kernel, the lean day kernel with the actor between its steps (one wavefront per 64
  * envs, the observation and the actions never leave LDS between the actor and the step); sng_graph_step_nodes
@@ -474,7 +479,7 @@ typedef struct SngMlpNetSpec {
  * sng_policy_set_weights, sng_policy_actions (one policy_net_kernel launch; a 64-64 MEAN net runs that kernel too),
  * sng_graph_create_policy and sng_policy_destroy.  Its captured days are always in node form, T x
  * (policy_net_kernel node, step node): SNG_GRAPH_POLICY_FUSED is accepted and gives nodes
- * (csrc/sng_step_plan.h, policy_net_day_form). */
+ * (csrc/sng_graph_form.h, policy_net_day_form). */
 int sng_policy_create_net(SngEnv *env, const SngMlpNetSpec *spec, SngPolicy **out);
 /* Host only: that contract on the CPU (csrc/sng_policy_net_host.h, mlp_net_host), over the chains' real terms.
  * For a 64-64 MEAN spec it gives what sng_policy_host_actions gives.  Validates as sng_policy_create_net and

@@ -651,7 +651,7 @@ int sng_step_host(SngEnv *env, const float *actions, float *obs, double *reward,
 
 int sng_step_kernel_name(const SngEnv *env, const SngInfo *info, char *buf, int32_t len) {
     if (!env || !buf || len < 1) return SNG_ERR_INVALID_ARGUMENT;
-    const int n = step_kernel_name(env->p, info_ptrs(info), buf, len);
+    const int n = step_plan_name(step_plan(env->p, info_diag(info_ptrs(info))), buf, len);
     return (n > 0 && n < len) ? SNG_OK : SNG_ERR_INVALID_ARGUMENT;
 }
 

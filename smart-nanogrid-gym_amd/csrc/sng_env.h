@@ -14,7 +14,7 @@
 #include "sng_layout.h"
 #include "sng_state_format.h"
 
-// The second day slot of an overlapped reset graph (sng_graph.cpp; sng_step_plan.h reset_overlapped): buffers of
+// The second day slot of an overlapped reset graph (sng_graph.cpp; sng_graph_form.h reset_overlapped): buffers of
 // its own for everything the device generator writes for a day -- the packed record timeline (`aux`, sized for a
 // packed day), the SoC seed the steps then run on, the PV ratio, the t = 0 penalty, the profile keys (where
 // Params::noise) and the requested-SoC plane (where enabled) -- and a day-return row [E] for graphs created
@@ -121,7 +121,7 @@ struct UploadedImage {
 // it read, which sng_policy_set_weights packs and uploads, and the clipped actions a captured step node reads.  It has
 // one of two forms: sng_policy_create's 64-64 actor (spec, image: sng_policy_host.h) or, with `net`,
 // sng_policy_create_net's actor of any width (net_spec, net_image: sng_policy_net_host.h).  What depends on the form
-// is decided in policy_weights_ok, policy_pack_image, launch_actor and policy_graph_fused below, and nowhere else.
+// is decided in policy_weights_ok, policy_pack_image, launch_actor and policy_kind below, and nowhere else.
 struct SngPolicy {
     SngEnv *env = nullptr;
     bool net = false;
@@ -158,11 +158,11 @@ struct SngNoise {
 
 struct SngGraph {
     SngEnv *env = nullptr;
-    SngPolicy *policy = nullptr;   // sng_graph_create_policy: the actor between the steps
     bool with_reset = false;
-    bool day_kernel = false;   // each day's steps are one day-kernel node (sng_step_day.h), not T step nodes
-    std::string day_kernel_name;   // that node's kernel as rocprofv3 names it (not a policy graph's); else empty
-    bool overlapped = false;   // day d + 1 is generated beside day d's steps (sng_step_plan.h reset_overlapped)
+    // from the graph's form (sng_graph_form.h graph_form)
+    int nodes_per_day = 0;     // the nodes that step a day (sng_graph_step_nodes): 1, T or 2 T
+    std::string day_kernel_name;   // a day-kernel node's kernel as rocprofv3 names it (not a policy graph's); else empty
+    bool overlapped = false;   // day d + 1 is generated beside day d's steps (reset_overlapped)
     sng::DayKey key{};   // the loaded-day encoding the graph's steps were captured for
     // the stream keys baked into the captured kernels' arguments: the device days a reset graph draws
     // and the PV-ratio / profile streams are those of this seed and env offset
@@ -277,11 +277,8 @@ inline hipError_t launch_actor(const SngPolicy *pol, const float *obs, const flo
     return pol->net ? launch_policy_net(pol->img.d, pol->net_image, obs, noise, actions, env_actions, E, stream)
                     : launch_policy(pol->img.d, pol->image, obs, noise, actions, env_actions, E, stream);
 }
-// The form of a policy's captured day: sng_step_plan.h decides it, per kind of policy.
-inline bool policy_graph_fused(const SngPolicy *pol, const Params &p, const InfoPtrs &ip, bool traj, bool step_nodes,
-                               bool force) {
-    return (pol->net ? policy_net_day_fused(p, ip, traj, step_nodes, force) : policy_day_fused(p, ip, traj, step_nodes, force)) != 0;
-}
+// What graph_form (sng_graph_form.h) asks about a graph's policy; null: the caller's actions.
+inline PolicyKind policy_kind(const SngPolicy *pol) { return !pol ? POLICY_NONE : pol->net ? POLICY_NET : POLICY_MLP; }
 
 inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 

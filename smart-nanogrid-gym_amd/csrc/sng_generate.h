@@ -283,7 +283,7 @@ __device__ __forceinline__ VehicleDraw draw_vehicle(const Params &p, GenStream &
 constexpr int kObsParts = kGenBlock / kWave;       // wavefronts per observation block (threads per env)
 constexpr int kObsEnvs = kGenBlock / kObsParts;    // envs per observation block
 constexpr int kObsBlocks = kGenBlock / kObsEnvs;   // observation blocks per 256 envs
-static_assert(kObsEnvs == kGenObsEnvs, "generator_fused (sng_step_plan.h) sizes the observation tile");
+static_assert(kObsEnvs == kGenObsEnvs, "generator_fused (sng_graph_form.h) sizes the observation tile");
 // obs == nullptr (the overlapped reset of a captured graph, sng_graph.cpp): the day's values are written -- ratio,
 // pen0, the profile keys, the SoC seed, the zeroed return -- and the row is not: step 0 overwrites it before a
 // caller could read it, and neither the observation buffer nor the BESS state is touched, which the day being
@@ -363,7 +363,7 @@ __device__ __forceinline__ void observe_day0(const Params &p, const DeviceState 
 // t = 0 observation (observe_day0).  The day counter is read here and advanced by the day's first step
 // (step_kernel, t = 0), so no block of this grid waits on another.  day_delta: the day drawn is the counter's
 // plus this -- 0 but in an overlapped reset graph, whose generators all run before anything advances the counter
-// (sng_step_plan.h day_shape).
+// (sng_graph_form.h day_shape).
 // The timeline records leave as streaming (nontemporal) stores: reset 24.5-24.7 -> 22.5-22.7 us per day
 // at 65,536 x 10 (A/B, one box), the steps' code and state staying in L2.  Diagnostic builds
 // (round 2's -DSNG_GX_* builds, in commits before 8be1f55) split the reset's time: without the t = 0 observation blocks 24.3-24.9 us

@@ -25,8 +25,10 @@
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "sng.h"
+#include "sng_graph_form.h"
 #include "sng_launch.h"
 #include "sng_layout.h"
 #include "sng_step_plan.h"
@@ -88,8 +90,6 @@ hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, 
 
 SNG_DIAG_SET_STAMPS   // diagnostic builds: sng_debug_set_stamps
 
-int step_lanes_supported(int n, int lanes) { return station_lanes_supported(n, lanes) ? 1 : 0; }
-
 // A plan's kernel and launch geometry.  The lean and the wide kernel share one signature (this step's table
 // constants by value, StepConst); the general kernel reads them through the tables pointer.
 typedef void (*ConstStepKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, StepConst, Params,
@@ -143,49 +143,31 @@ static StepLaunch general_launch_lanes(const StepPlan &pl, const Params &p, int6
                            : general_launch<NC, 1>(pl, p, E);
 }
 
+// Calls f with the run-time value `nc` (a station size, mostly) as a compile-time constant (an integral_constant) where
+// it is one of Ns; false, and no call, for any other value.  with_lean_size: the lean sizes of kStationSizes (sng_step_plan.h).
+template <int... Ns, class F>
+static bool with_size(int nc, F f) {
+    return ((nc == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+template <class F>
+static bool with_lean_size(int nc, F f) {
+    return with_size<1, 2, 4, 8, 10, 16>(nc, f);
+}
+
 // The map from a plan to its kernel: one case per compiled station size of kStationSizes (sng_step_plan.h).  A
 // plan without a case here has no kernel (launch_step fails; tests/test_step_plan_cpu.py holds every name a
 // plan can give against the code object's symbols).
 static StepLaunch step_launch(const StepPlan &pl, const Params &p, int64_t E) {
+    StepLaunch l;
     switch (pl.family) {
-        case STEP_LEAN:
-            switch (pl.nc) {
-                case 1: return lean_launch<1>(pl, E);
-                case 2: return lean_launch<2>(pl, E);
-                case 4: return lean_launch<4>(pl, E);
-                case 8: return lean_launch<8>(pl, E);
-                case 10: return lean_launch<10>(pl, E);
-                case 16: return lean_launch<16>(pl, E);
-            }
-            break;
-        case STEP_WIDE:
-            switch (pl.nc) {
-                case 10: return wide_launch<10>(pl, E);
-                case 50: return wide_launch<50>(pl, E);
-            }
-            break;
-        case STEP_GENERAL:
-            switch (pl.nc) {
-                case 0: return general_launch<0, 1>(pl, p, E);
-                case 1: return general_launch<1, 1>(pl, p, E);
-                case 2: return general_launch_lanes<2>(pl, p, E);
-                case 4: return general_launch_lanes<4>(pl, p, E);
-                case 8: return general_launch_lanes<8>(pl, p, E);
-                case 10: return general_launch_lanes<10>(pl, p, E);
-                case 16: return general_launch_lanes<16>(pl, p, E);
-                case 50: return general_launch_lanes<50>(pl, p, E);
-            }
+        case STEP_LEAN: with_lean_size(pl.nc, [&](auto n) { l = lean_launch<decltype(n)::value>(pl, E); }); break;
+        case STEP_WIDE: with_size<10, 50>(pl.nc, [&](auto n) { l = wide_launch<decltype(n)::value>(pl, E); }); break;
+        case STEP_GENERAL:   // a runtime N and one charger run one lane per env only
+            if (!with_size<0, 1>(pl.nc, [&](auto n) { l = general_launch<decltype(n)::value, 1>(pl, p, E); }))
+                with_size<2, 4, 8, 10, 16, 50>(pl.nc, [&](auto n) { l = general_launch_lanes<decltype(n)::value>(pl, p, E); });
             break;
     }
-    return {};
-}
-
-// The step kernel writes the diagnostics (DIAG) when any SngInfo array other than the flags and the
-// day return is given.
-static bool info_diag(const InfoPtrs &info) {
-    return info.grid_power || info.p_charge || info.p_discharge || info.bess_soc || info.pen_vehicle ||
-           info.pen_battery || info.grid_cost || info.total_cost || info.solar || info.bess_power ||
-           info.bess_calc_power || info.nonexistent || info.bess_initial || info.charger_power || info.vehicle_soc;
+    return l;
 }
 
 hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
@@ -202,11 +184,11 @@ hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &in
                          vec_io, k, p, s, info);
 }
 
-// The day kernel of a plan (day_kernel_of, sng_step_plan.h): day_wide_kernel for the packed days of the wide
-// family's 10-charger station (day_station_kernel where day_station_selected says so), day_lean_kernel for the
-// lean family's plans (sng_step_day.h); every other plan has none.  N = 50 is not compiled: with every charger's
-// SoC kept next to the step's 239 VGPRs it spills (325-423 VGPR spills, 0.8-1 KB of scratch), so config 5's days
-// stay T step nodes.
+// The day kernels (sng_step_day.h): day_wide_kernel and day_station_kernel for the packed days of the wide family's
+// 10-charger station, day_lean_kernel for the lean family's plans; every other plan has none.  Which of them a
+// captured day runs is decided before launch_day is called (sng_graph_form.h graph_form).  N = 50 is not compiled:
+// with every charger's SoC kept next to the step's 239 VGPRs it spills (325-423 VGPR spills, 0.8-1 KB of scratch),
+// so config 5's days stay T step nodes.
 typedef void (*DayKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, Params, DeviceState,
                           InfoPtrs);
 typedef void (*DayLeanKernel)(const float *, float *, double *, uint8_t *, int64_t, int, int, int, int64_t, int64_t,
@@ -228,37 +210,27 @@ static DayLeanKernel day_lean_entry() {
 }
 template <int NC>
 static StepLaunch day_lean_launch(const StepPlan &pl, int64_t E, DayLeanKernel &kern) {
-    kern = day_lean_entry<NC, false, false>();
-    if (pl.pk && pl.req) kern = day_lean_entry<NC, true, true>();
-    else if (pl.pk) kern = day_lean_entry<NC, true, false>();
-    else if (pl.req) kern = day_lean_entry<NC, false, true>();
+    const DayLeanKernel k[2][2] = {{day_lean_entry<NC, false, false>(), day_lean_entry<NC, false, true>()},
+                                   {day_lean_entry<NC, true, false>(), day_lean_entry<NC, true, true>()}};
+    kern = k[pl.pk][pl.req];
     return {nullptr, nullptr, blocks_for(E, kLeanBlock), dim3(kLeanBlock), LeanLds<NC>::BYTES};
 }
 
-int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory) {
-    return day_kernel_of(step_plan(p, info_diag(info)), trajectory) != DAY_NONE ? 1 : 0;
-}
-
-int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
-                           size_t *generator_lds, bool day_kernel, bool generic_day) {
+hipError_t launch_day(DayNode node, const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act,
+                      float *obs, double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
+                      int64_t obs_step, int64_t out_step) {
     const StepPlan pl = step_plan(p, info_diag(info));
-    if (!reset_overlapped(pl, p, days, trajectory, serial, force)) return 0;
-    const bool station_day = day_kernel && day_kernel_of(pl, trajectory) == DAY_WIDE && day_station_selected(pl, p, generic_day);
-    if (generator_lds) *generator_lds = overlapped_generator_lds(pl, station_day);
-    return 1;
-}
-
-hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
-                      int64_t obs_step, int64_t out_step, bool generic_day) {
-    const StepPlan pl = step_plan(p, info_diag(info));
+    // the node graph_form decided is one of the plan's family (and the station kernel only its own station's)
     const DayFamily fam = day_kernel_of(pl, obs_step != 0 || out_step != 0);
-    if (fam == DAY_NONE) return hipErrorNotSupported;
+    const bool wide = node == DAY_KERNEL_WIDE || node == DAY_KERNEL_STATION;
+    if (fam == DAY_NONE || (fam == DAY_WIDE) != wide || (fam == DAY_LEAN) != (node == DAY_KERNEL_LEAN) ||
+        (node == DAY_KERNEL_STATION && !day_station_fixed(pl, p)))
+        return hipErrorNotSupported;
     if (t0 < 0 || nt < 1 || t0 + nt > p.T) return hipErrorInvalidValue;
-    if (fam == DAY_WIDE) {
+    if (wide) {
         DayKernel kern = nullptr;
         const StepLaunch l = day_launch<10>(pl, E, kern);
-        if (day_station_selected(pl, p, generic_day)) {
+        if (node == DAY_KERNEL_STATION) {
             static_assert(kDayStationN == 10 && kWideLanes == 2, "day_launch<10>'s geometry");
             const DayStationArgs a{act, obs, reward, done, E, t0, nt, vec_io, p.bump_day, p.dt_f, p.ev_power_f, p.ev_eff_f,
                                    p.dt, p.rdt, p.bess_cap, p.bess_pmax_ch, p.bess_pmax_dis, p.bess_eff_ch,
@@ -274,30 +246,12 @@ hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &inf
     }
     DayLeanKernel kern = nullptr;
     StepLaunch l;
-    switch (pl.nc) {   // the lean sizes of kStationSizes
-        case 1: l = day_lean_launch<1>(pl, E, kern); break;
-        case 2: l = day_lean_launch<2>(pl, E, kern); break;
-        case 4: l = day_lean_launch<4>(pl, E, kern); break;
-        case 8: l = day_lean_launch<8>(pl, E, kern); break;
-        case 10: l = day_lean_launch<10>(pl, E, kern); break;
-        case 16: l = day_lean_launch<16>(pl, E, kern); break;
-    }
+    with_lean_size(pl.nc, [&](auto n) { l = day_lean_launch<decltype(n)::value>(pl, E, kern); });
     if (!kern) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
     // every step's observation block 16 B aligned, or none is promised to be
     if (obs_step % 4 != 0) vec_io = 0;
     return launch_kernel(kern, l.grid, l.block, l.lds, stream, nullptr, nullptr, act, obs, reward, done, E, t0, nt,
                          vec_io, obs_step, out_step, p, s, info);
-}
-
-int day_kernel_name(const Params &p, const InfoPtrs &info, bool trajectory, bool generic_day, char *buf, int len) {
-    const StepPlan pl = step_plan(p, info_diag(info));
-    if (day_kernel_of(pl, trajectory) == DAY_WIDE && day_station_selected(pl, p, generic_day))
-        return day_station_name(buf, len);
-    return day_plan_name(pl, trajectory, buf, len);
-}
-
-int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len) {
-    return step_plan_name(step_plan(p, info_diag(info)), buf, len);
 }
 
 hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
@@ -318,7 +272,7 @@ hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, do
 // while its [256][obs_dim] LDS tile stays small next to the vehicle lists (N <= 16: at most 42 KB,
 // a few generator workgroups per CU still fit); wider stations keep profile_kernel and
 // observe0_kernel as separate launches behind the generator.
-// day_delta != 0 or obs == nullptr: an overlapped reset graph's generator (sng_step_plan.h reset_overlapped), the
+// day_delta != 0 or obs == nullptr: an overlapped reset graph's generator (sng_graph_form.h reset_overlapped), the
 // one-launch form only.
 hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed, int64_t E, int i4, int i10, int i1,
                            float *obs, double *ep_return, int vec_io, hipStream_t stream, hipEvent_t ev_start,
@@ -381,12 +335,9 @@ static void launch_ref_day2(const Params &p, const DeviceState &s, const RefStre
     const int64_t per = (int64_t)envs * kRefGroups;   // envs per workgroup
     const dim3 grid((unsigned)((E + per - 1) / per)), block(kRefBlock);
     const size_t lds = ref_day2_lds_bytes(REQ, envs);
-    switch (envs) {
-        case 8: launch_ref_day2_envs<TT, REQ, 8>(grid, block, lds, stream, p, s, rs, E, i4, i10, i1); break;
-        case 16: launch_ref_day2_envs<TT, REQ, 16>(grid, block, lds, stream, p, s, rs, E, i4, i10, i1); break;
-        case 32: launch_ref_day2_envs<TT, REQ, 32>(grid, block, lds, stream, p, s, rs, E, i4, i10, i1); break;
-        default: launch_ref_day2_envs<TT, REQ, 64>(grid, block, lds, stream, p, s, rs, E, i4, i10, i1); break;
-    }
+    with_size<8, 16, 32, 64>(envs, [&](auto n) {
+        launch_ref_day2_envs<TT, REQ, decltype(n)::value>(grid, block, lds, stream, p, s, rs, E, i4, i10, i1);
+    });
 }
 
 hipError_t launch_ref_seed(const RefStreams &rs, uint64_t seed0, int64_t E, hipStream_t stream) {
@@ -410,13 +361,9 @@ hipError_t launch_ref_day(const Params &p, const DeviceState &s, const RefStream
         if (e != hipSuccess) return e;
     }
     const bool req = p.req_stream != 0;
-    if (p.T == 24) {
-        if (req) launch_ref_day2<24, true>(p, s, rs, E, i4, i10, i1, stream);
-        else launch_ref_day2<24, false>(p, s, rs, E, i4, i10, i1, stream);
-    } else {
-        if (req) launch_ref_day2<0, true>(p, s, rs, E, i4, i10, i1, stream);
-        else launch_ref_day2<0, false>(p, s, rs, E, i4, i10, i1, stream);
-    }
+    auto launch = p.T == 24 ? (req ? launch_ref_day2<24, true> : launch_ref_day2<24, false>)
+                            : (req ? launch_ref_day2<0, true> : launch_ref_day2<0, false>);
+    launch(p, s, rs, E, i4, i10, i1, stream);
     return hipGetLastError();
 }
 
@@ -431,14 +378,6 @@ hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t am
     return hipGetLastError();
 }
 
-int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force) {
-    return policy_day_form(step_plan(p, info_diag(info)), trajectory, step_nodes, force) == POLICY_FUSED ? 1 : 0;
-}
-
-int policy_net_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force) {
-    return policy_net_day_form(step_plan(p, info_diag(info)), trajectory, step_nodes, force) == POLICY_FUSED ? 1 : 0;
-}
-
 typedef void (*PolicyDayKernel)(const float *, PolicyImage, const float *, int64_t, int, const float *, float *, float *,
                                 double *, uint8_t *, int64_t, int, int, int, int, int64_t, int64_t, int64_t, Params,
                                 DeviceState, InfoPtrs);
@@ -450,10 +389,9 @@ static PolicyDayKernel policy_day_entry() {
 }
 template <int NC>
 static StepLaunch policy_day_launch(const StepPlan &pl, int64_t E, PolicyDayKernel &kern) {
-    kern = policy_day_entry<NC, false, false>();
-    if (pl.pk && pl.req) kern = policy_day_entry<NC, true, true>();
-    else if (pl.pk) kern = policy_day_entry<NC, true, false>();
-    else if (pl.req) kern = policy_day_entry<NC, false, true>();
+    const PolicyDayKernel k[2][2] = {{policy_day_entry<NC, false, false>(), policy_day_entry<NC, false, true>()},
+                                     {policy_day_entry<NC, true, false>(), policy_day_entry<NC, true, true>()}};
+    kern = k[pl.pk][pl.req];
     return {nullptr, nullptr, blocks_for(E, kLeanBlock), dim3(kLeanBlock), PolicyDayLds<NC>::BYTES};
 }
 
@@ -462,18 +400,11 @@ hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPt
                              float *actions_out, double *reward, uint8_t *done, int64_t E, int vec_io,
                              hipStream_t stream, int64_t obs_step, int64_t out_step, int64_t act_step) {
     const StepPlan pl = step_plan(p, info_diag(info));
-    if (policy_day_form(pl, obs_step != 0 || out_step != 0, false, true) != POLICY_FUSED) return hipErrorNotSupported;
     if (m.O != p.obs_dim || m.A != p.act_dim) return hipErrorInvalidValue;
     PolicyDayKernel kern = nullptr;
     StepLaunch l;
-    switch (pl.nc) {   // the lean sizes of kStationSizes
-        case 1: l = policy_day_launch<1>(pl, E, kern); break;
-        case 2: l = policy_day_launch<2>(pl, E, kern); break;
-        case 4: l = policy_day_launch<4>(pl, E, kern); break;
-        case 8: l = policy_day_launch<8>(pl, E, kern); break;
-        case 10: l = policy_day_launch<10>(pl, E, kern); break;
-        case 16: l = policy_day_launch<16>(pl, E, kern); break;
-    }
+    if (pl.family == STEP_LEAN)
+        with_lean_size(pl.nc, [&](auto n) { l = policy_day_launch<decltype(n)::value>(pl, E, kern); });
     if (!kern) return hipErrorInvalidDeviceFunction;   // a plan without a compiled kernel
     // every step's block 16 B aligned, or none is promised to be
     const int64_t noise_step = noise ? E * (int64_t)p.act_dim : 0;
@@ -531,11 +462,8 @@ hipError_t launch_policy_net(const float *img, const NetImage &m, const float *o
     if (lds > kNetMaxLds || m.N3 > kNetMaxAct) return hipErrorInvalidValue;   // what net_spec_check refuses
     if (lds > 64u * 1024u && policy_kernels_init() != hipSuccess) return policy_kernels_init();
     const dim3 grid = blocks_for(E, kNetRows), block(kNetBlock);
-    return m.activation == POLICY_RELU
-               ? launch_kernel(policy_net_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise,
-                               actions, env_actions, E)
-               : launch_kernel(policy_net_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise,
-                               actions, env_actions, E);
+    auto kern = m.activation == POLICY_RELU ? policy_net_kernel<false> : policy_net_kernel<true>;
+    return launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, img, m, obs, noise, actions, env_actions, E);
 }
 
 // rollout_gae_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises the policy kernels': two observation
@@ -559,13 +487,9 @@ hipError_t launch_rollout_gae(const float *img, const PpoImage &m, const SngPpoR
     const int vec_noise = (aligned16(noise) && (E * (int64_t)m.head.A) % 4 == 0) ? 1 : 0;
     const dim3 grid((unsigned)((E + kWave - 1) / kWave), (unsigned)r.days), block(kPolicyBlock);
     const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
-    return m.v.activation == POLICY_RELU
-               ? launch_kernel(rollout_gae_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs,
-                               r.reward, r.done, noise, r.values, r.advantages, r.returns, r.logp, E, T, g, gl,
-                               two ? 1 : 0, vec_obs, vec_noise)
-               : launch_kernel(rollout_gae_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs,
-                               r.reward, r.done, noise, r.values, r.advantages, r.returns, r.logp, E, T, g, gl,
-                               two ? 1 : 0, vec_obs, vec_noise);
+    auto kern = m.v.activation == POLICY_RELU ? rollout_gae_kernel<false> : rollout_gae_kernel<true>;
+    return launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, img, m, r.obs, r.reward, r.done, noise, r.values,
+                         r.advantages, r.returns, r.logp, E, T, g, gl, two ? 1 : 0, vec_obs, vec_noise);
 }
 
 // value_net_kernel's dynamic-LDS limit, raised once as policy_kernels_init raises policy_net_kernel's: the same tiles,
@@ -589,22 +513,17 @@ hipError_t launch_ppo_net(const float *img, const PpoNetImage &m, const SngPpoRo
         return hipErrorInvalidValue;
     if (lds > 64u * 1024u && ppo_net_kernels_init() != hipSuccess) return ppo_net_kernels_init();
     const dim3 grid((unsigned)ppo_net_blocks(rows)), block(kNetBlock);
-    const hipError_t e = m.v.activation == POLICY_RELU
-                             ? launch_kernel(value_net_kernel<false>, grid, block, lds, stream, nullptr, nullptr, img,
-                                             m.v, r.obs, r.values, rows)
-                             : launch_kernel(value_net_kernel<true>, grid, block, lds, stream, nullptr, nullptr, img,
-                                             m.v, r.obs, r.values, rows);
+    auto kern = m.v.activation == POLICY_RELU ? value_net_kernel<false> : value_net_kernel<true>;
+    const hipError_t e = launch_kernel(kern, grid, block, lds, stream, nullptr, nullptr, img, m.v, r.obs, r.values, rows);
     if (e != hipSuccess) return e;
     const dim3 sgrid((unsigned)((E + kScanBlock - 1) / kScanBlock), (unsigned)scan_rows), sblock(kScanBlock);
     const float g = ppo_gamma_f32(r.gamma), gl = ppo_gamma_lambda_f32(r.gamma, r.gae_lambda);
     const float *values = r.values;
     const GaussHead &h = m.head;
-    return noise ? launch_kernel(gae_scan_kernel<true>, sgrid, sblock, gae_scan_lds_bytes(h.A), stream, nullptr, nullptr, img,
-                                 h.log_std, h.inv_std, (int)h.A, r.reward, r.done, noise, values, r.advantages,
-                                 r.returns, r.logp, E, T, (int)r.days, g, gl)
-                 : launch_kernel(gae_scan_kernel<false>, sgrid, sblock, 0, stream, nullptr, nullptr, img, h.log_std,
-                                 h.inv_std, (int)h.A, r.reward, r.done, noise, values, r.advantages, r.returns, r.logp,
-                                 E, T, (int)r.days, g, gl);
+    auto scan = noise ? gae_scan_kernel<true> : gae_scan_kernel<false>;
+    return launch_kernel(scan, sgrid, sblock, noise ? gae_scan_lds_bytes(h.A) : 0, stream, nullptr, nullptr, img, h.log_std,
+                         h.inv_std, (int)h.A, r.reward, r.done, noise, values, r.advantages, r.returns, r.logp, E, T,
+                         (int)r.days, g, gl);
 }
 
 // A source's fill and, behind it, its counter's bump: grid x over the row's groups of four elements, y over the blocks.
@@ -618,12 +537,9 @@ hipError_t launch_noise_fill(const SngNoiseSpec &spec, const float *params, uint
     const dim3 grid((unsigned)blocks, (unsigned)(days < kNoiseMaxGridDays ? days : kNoiseMaxGridDays)), block(kNoiseBlock);
     const int vec = (aligned16(out) && row % 4 == 0) ? 1 : 0;
     const float theta = (float)spec.theta, dt = (float)spec.dt;
-    const hipError_t e =
-        spec.kind == SNG_NOISE_OU
-            ? launch_kernel(action_noise_kernel<SNG_NOISE_OU>, grid, block, 0, stream, nullptr, nullptr, params,
-                            (const uint64_t *)counter, spec.seed, env_offset, theta, dt, out, (int)days, T, E, A, vec)
-            : launch_kernel(action_noise_kernel<SNG_NOISE_GAUSSIAN>, grid, block, 0, stream, nullptr, nullptr, params,
-                            (const uint64_t *)counter, spec.seed, env_offset, theta, dt, out, (int)days, T, E, A, vec);
+    auto kern = spec.kind == SNG_NOISE_OU ? action_noise_kernel<SNG_NOISE_OU> : action_noise_kernel<SNG_NOISE_GAUSSIAN>;
+    const hipError_t e = launch_kernel(kern, grid, block, 0, stream, nullptr, nullptr, params, (const uint64_t *)counter,
+                                       spec.seed, env_offset, theta, dt, out, (int)days, T, E, A, vec);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(noise_bump_kernel, dim3(1), dim3(1), 0, stream, counter, (uint64_t)days);
     return hipGetLastError();
@@ -699,14 +615,11 @@ hipError_t launch_learn_gemm(const LearnGemm &g, int epilogue, hipStream_t strea
     const dim3 grid((unsigned)((g.N + kNetTile - 1) / kNetTile), (unsigned)((g.M + per - 1) / per), (unsigned)segs);
     if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
     const dim3 block(kLearnBlock);
-    switch (epilogue) {
-    case LEARN_EPI_NONE: return launch_kernel(learn_gemm_kernel<LEARN_EPI_NONE>, grid, block, 0, stream, nullptr, nullptr, g);
-    case LEARN_EPI_RELU: return launch_kernel(learn_gemm_kernel<LEARN_EPI_RELU>, grid, block, 0, stream, nullptr, nullptr, g);
-    case LEARN_EPI_MASK: return launch_kernel(learn_gemm_kernel<LEARN_EPI_MASK>, grid, block, 0, stream, nullptr, nullptr, g);
-    case LEARN_EPI_TANH: return launch_kernel(learn_gemm_kernel<LEARN_EPI_TANH>, grid, block, 0, stream, nullptr, nullptr, g);
-    case LEARN_EPI_DTANH: return launch_kernel(learn_gemm_kernel<LEARN_EPI_DTANH>, grid, block, 0, stream, nullptr, nullptr, g);
-    }
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;   // no such epilogue
+    with_size<LEARN_EPI_NONE, LEARN_EPI_RELU, LEARN_EPI_MASK, LEARN_EPI_TANH, LEARN_EPI_DTANH>(epilogue, [&](auto epi) {
+        e = launch_kernel(learn_gemm_kernel<decltype(epi)::value>, grid, block, 0, stream, nullptr, nullptr, g);
+    });
+    return e;
 }
 
 // dq [rows] and the loss (learn_loss_kernel); y is the critic's, null with `actor`

@@ -1,11 +1,13 @@
 // sng_launch.h -- what the host translation units (through sng_env.h) call in sng_kernels.hip: the launch
 // wrappers; the kernels they launch live in the headers that file includes.  They all include it, so a changed
-// signature is a compile error in one of them; default arguments live here only.
+// signature is a compile error in one of them; default arguments live here only.  Launches only: what a plan's
+// graph looks like is answered by sng_graph_form.h, before anything is launched.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "sng_ddpg_host.h"
 #include "sng_ddpg_learn_host.h"
+#include "sng_graph_form.h"
 #include "sng_layout.h"
 #include "sng_noise_host.h"
 #include "sng_policy_host.h"
@@ -22,19 +24,16 @@ inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
 hipError_t launch_step(const Params &p, const DeviceState &s, const InfoPtrs &info, const Tables &tab,
                        const float *act, float *obs, double *reward, uint8_t *done, int64_t E, int t, int vec_io,
                        hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-// Steps t0 .. t0 + nt - 1 of the loaded day in one launch (sng_step_day.h); `act` is step t0's block of nt
-// consecutive [E][act_dim] blocks.  hipErrorNotSupported for a plan without a day kernel
-// (day_kernel_available == 0): the caller launches the steps one by one.
+// Steps t0 .. t0 + nt - 1 of the loaded day in one launch (sng_step_day.h) of the day kernel `node` names, which
+// graph_form decided (DAY_KERNEL_LEAN, DAY_KERNEL_WIDE or DAY_KERNEL_STATION); `act` is step t0's block of nt
+// consecutive [E][act_dim] blocks.  hipErrorNotSupported for any other node and for a node that is not the plan's
+// (day_kernel_of; the station kernel: day_station_fixed).
 // obs_step / out_step: floats from one step's observation block to the next and elements from one step's reward
-// and done block to the next, when every step's outputs are kept (`trajectory`, which only some plans' day
-// kernels can do: sng_step_plan.h day_kernel_of); 0: every step overwrites the same blocks.
-// generic_day: the wide plan's generic kernel also where its station-fixed one would run (sng_step_plan.h).
-int day_kernel_available(const Params &p, const InfoPtrs &info, bool trajectory = false);
-hipError_t launch_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act, float *obs,
-                      double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
-                      int64_t obs_step = 0, int64_t out_step = 0, bool generic_day = false);
-// The name rocprofv3 reports for the kernel launch_day would launch (an empty string where the plan has none).
-int day_kernel_name(const Params &p, const InfoPtrs &info, bool trajectory, bool generic_day, char *buf, int len);
+// and done block to the next, when every step's outputs are kept (`trajectory`, which only the lean day kernel
+// can do: sng_step_plan.h day_kernel_of); 0: every step overwrites the same blocks.
+hipError_t launch_day(DayNode node, const Params &p, const DeviceState &s, const InfoPtrs &info, const float *act,
+                      float *obs, double *reward, uint8_t *done, int64_t E, int t0, int nt, int vec_io, hipStream_t stream,
+                      int64_t obs_step = 0, int64_t out_step = 0);
 hipError_t launch_observe0(const Params &p, const DeviceState &s, float *obs, double *ep_return, int64_t E,
                            int vec_io, hipStream_t stream, int mode, int64_t replay, const RefStreams *ps = nullptr,
                            int py = 0);
@@ -42,11 +41,6 @@ hipError_t launch_generate(const Params &p, const DeviceState &s, uint64_t seed,
                            float *obs, double *ep_return, int vec_io, hipStream_t stream,
                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int day_delta = 0,
                            size_t min_lds = 0);
-// Whether a reset graph of `days` days over this plan is captured overlapped (sng_step_plan.h reset_overlapped),
-// and then the dynamic LDS its generators ask for at least (overlapped_generator_lds).  day_kernel: the graph's days
-// are day-kernel nodes; generic_day as launch_day's (beside day_station_kernel the generators ask for less).
-int reset_graph_overlapped(const Params &p, const InfoPtrs &info, int days, bool trajectory, bool serial, bool force,
-                           size_t *generator_lds, bool day_kernel = false, bool generic_day = false);
 hipError_t launch_profiles(const Params &p, const DeviceState &s, int64_t E, hipStream_t stream);
 hipError_t launch_bump_day(const DeviceState &s, hipStream_t stream, uint64_t amount = 1);
 hipError_t launch_probe_copy(const void *in, void *out, int64_t nr, int64_t nw, hipStream_t stream, hipEvent_t a,
@@ -66,14 +60,10 @@ hipError_t launch_policy_net(const float *img, const NetImage &m, const float *o
 // The policy kernels' dynamic-LDS limit, raised once (stations above 45 chargers need more than 64 KB); called by
 // sng_policy_create so that no capture is the first to ask.
 hipError_t policy_kernels_init();
-// 1: a captured policy day of this plan is one fused node (sng_step_plan.h policy_day_form), 0: T x (policy, step)
-int policy_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force);
-// the same for a policy made by sng_policy_create_net (sng_step_plan.h policy_net_day_form: always 0)
-int policy_net_day_fused(const Params &p, const InfoPtrs &info, bool trajectory, bool step_nodes, bool force);
-// A whole day with the actor between the steps in one launch (sng_policy.h, day_lean_policy_kernel), for a plan
-// with the fused form (hipErrorNotSupported otherwise).  noise: T blocks or null; obs0: the day's t = 0 observation
-// block; obs, reward, done: step 0's blocks, obs_step / out_step as launch_day's; actions_out: step 0's block of a,
-// act_step floats to the next step's (0: one block).
+// A whole day with the actor between the steps in one launch (sng_policy.h, day_lean_policy_kernel), where graph_form
+// decided DAY_POLICY_FUSED (hipErrorInvalidDeviceFunction for a plan without that kernel).  noise: T blocks or null;
+// obs0: the day's t = 0 observation block; obs, reward, done: step 0's blocks, obs_step / out_step as launch_day's;
+// actions_out: step 0's block of a, act_step floats to the next step's (0: one block).
 hipError_t launch_policy_day(const Params &p, const DeviceState &s, const InfoPtrs &info, const float *img,
                              const PolicyImage &m, const float *noise, const float *obs0, float *obs,
                              float *actions_out, double *reward, uint8_t *done, int64_t E, int vec_io,
@@ -117,8 +107,5 @@ hipError_t launch_learn_gemm(const LearnGemm &g, int epilogue, hipStream_t strea
 hipError_t launch_learn_loss(bool actor, const float *q, const float *y, float *dq, float *loss, int64_t rows,
                              hipStream_t stream);
 hipError_t launch_learn_step(const LearnStep &s, bool adam, hipStream_t stream);
-int step_lanes_supported(int n, int lanes);
-// The name rocprofv3 reports for the step kernel launch_step would dispatch next.
-int step_kernel_name(const Params &p, const InfoPtrs &info, char *buf, int len);
 
 }  // namespace sng

@@ -1,7 +1,7 @@
 // sng_step_plan.h -- which step kernel a handle's Params select, and which day kernel a captured day of that plan
-// runs (day_kernel_of), each decided once.
+// runs (day_kernel_of), each decided once.  What a captured graph makes of these answers is sng_graph_form.h's.
 //
-// launch_step (sng_kernels.hip) dispatches the kernel a plan names and step_kernel_name formats the same plan
+// launch_step (sng_kernels.hip) dispatches the kernel a plan names and step_plan_name formats the same plan
 // as the name rocprofv3 reports, so the two cannot disagree.  Host only, no HIP types: it compiles with plain
 // g++ (tests/native/step_plan_check.cpp lists the name of every configuration on the CPU).
 #pragma once
@@ -82,7 +82,7 @@ inline StepPlan step_plan(const Params &p, bool diag) {
 }
 
 // Which day kernel (sng_step_day.h) a plan has: a captured day's T steps as one launch.  Decided here and nowhere
-// else: day_kernel_available and launch_day (sng_kernels.hip) both ask this.
+// else: graph_form (sng_graph_form.h) asks this, and launch_day (sng_kernels.hip) launches what it decided.
 //   - the lean family's plans run day_lean_kernel<NC, PK, REQ>, at every compiled lean size and for both timeline
 //     encodings (but day_lean_compiled, below);
 //   - the wide family's packed days at N = 10 run day_wide_kernel<10, 2, REQ, NOISE>.  That kernel keeps no
@@ -128,85 +128,12 @@ inline bool day_station_selected(const StepPlan &pl, const Params &p, bool gener
 inline int day_station_name(char *buf, int len) {
     return snprintf(buf, (size_t)len, "void sng::day_station_kernel<%d, %d>", kDayStationN, kWideLanes);
 }
-// The form of a captured day with the MLP actor in the loop (sng_graph_create_policy).  Decided here and nowhere
-// else.  POLICY_NODES: T x (policy_kernel node, step node), the step nodes being the plan's own step kernel.
-// POLICY_FUSED: day_lean_policy_kernel<NC, PK, REQ> (sng_policy.h), the actor between the steps of the plan's lean day
-// kernel, one node a day.  It exists where day_lean_kernel does and policy_day_compiled says so (zero scratch, zero
-// VGPR spills: tests/test_policy_kernel_resources.py); the wide N = 10 and N = 50 plans, the general kernel's
-// stations, any diagnostics and SNG_GRAPH_STEP_NODES (`step_nodes`) take nodes.  Where it exists it is the default
-// only where its day measured shorter than the node form's by more than the node form's own spread
-// (policy_day_faster; profiles/policy_day_ab.txt); SNG_GRAPH_POLICY_FUSED (`force`: A/B runs
-// and tests) takes it wherever it is compiled.
-enum PolicyDayForm : int { POLICY_NODES, POLICY_FUSED };
+// Whether day_lean_policy_kernel<NC, PK, REQ> (sng_policy.h), the lean day kernel with the MLP actor between its steps,
+// is compiled for a plan (zero scratch, zero VGPR spills: tests/test_policy_kernel_resources.py) and whether its day
+// measured shorter than T x (actor node, step node) (profiles/policy_day_ab.txt).  Which form a
+// captured policy day takes is sng_graph_form.h's (policy_day_form).
 constexpr bool policy_day_compiled(int nc, bool pk, bool req) { return day_lean_compiled(nc, pk, req); }
 constexpr bool policy_day_faster(int /*nc*/) { return false; }
-inline PolicyDayForm policy_day_form(const StepPlan &pl, bool trajectory, bool step_nodes, bool force = false) {
-    if (step_nodes || day_kernel_of(pl, trajectory) != DAY_LEAN || !policy_day_compiled(pl.nc, pl.pk, pl.req))
-        return POLICY_NODES;
-    return (policy_day_faster(pl.nc) || force) ? POLICY_FUSED : POLICY_NODES;
-}
-// A policy made by sng_policy_create_net (policy_net_kernel, sng_policy_net.h) has no fused day: its actor is a
-// workgroup of four wavefronts on 64 rows with up to 160 KB of LDS, which no day kernel's wavefront can carry between
-// its steps.  Every plan takes nodes, T x (policy_net_kernel node, step node), whatever is forced.
-inline PolicyDayForm policy_net_day_form(const StepPlan & /*pl*/, bool /*trajectory*/, bool /*step_nodes*/,
-                                         bool /*force*/ = false) {
-    return POLICY_NODES;
-}
-// A device-RNG reset is one launch -- the t = 0 observation as extra blocks of the generator's grid -- while the
-// observation blocks' [kGenObsEnvs][obs_dim] LDS tile stays small next to the vehicle lists (32 KB: up to 60
-// chargers); wider stations run profile_kernel and observe0_kernel behind the generator (launch_generate).
-constexpr int kGenObsEnvs = 64;
-inline bool generator_fused(const Params &p) { return (size_t)((kGenObsEnvs * p.obs_dim + 3) & ~3) * 4 <= 32 * 1024; }
-
-// The shape of a captured reset graph (sng_graph_create with SNG_GRAPH_RESET).  Serial: every day's generator, then
-// its steps, in one chain.  Overlapped: day d + 1 is generated into a second day slot while day d is stepped.
-// Decided here and nowhere else, for a plan and a graph: at least two days, no kept trajectory (the generator
-// would have to write every day's t = 0 observation; without one, step 0 overwrites that row, so the overlapped
-// generator skips it), the one-launch generator, no SNG_GRAPH_SERIAL_RESET -- and a plan whose day measured
-// shorter that way (device time per day at 65,536 envs, serial -> overlapped, profiles/overlapped_reset_ab.txt),
-// whether its day is a day-kernel node or T step nodes:
-//   - the wide family's 10-charger station: 93.3 -> 87.0 us (with the requested-SoC stream 126.3 -> 123.1).
-// Not shorter, so serial unless forced (SNG_GRAPH_OVERLAPPED_RESET, `force`: A/B runs and tests):
-//   - the lean family's 8 chargers: 119.6 -> 112.6 - 117.3 us between HIP events, but bench.py's wall time 0.4 -
-//     1.2 % behind the parent's; 4 chargers 68.5 -> 70.8 us; 16 chargers 184.8 -> 240.2 us;
-//   - config 5's 50 chargers, 2.12 -> 2.15 ms: its step kernel's eight wavefronts take a CU's whole LDS, so a
-//     generator workgroup that gets in keeps a wavefront out;
-//   - every plan that was not measured.
-inline bool reset_overlapped(const StepPlan &pl, const Params &p, int days, bool trajectory, bool serial,
-                             bool force = false) {
-    const bool faster = pl.family == STEP_WIDE && pl.nc == 10;
-    return days >= 2 && !trajectory && !serial && generator_fused(p) && (faster || force);
-}
-// The dynamic LDS an overlapped graph's generator workgroups ask for at least (bytes; 0: what they need).  Beside
-// the wide family's day, which has exactly two wavefronts per SIMD to run and 40 KB of tiles per CU to place, the
-// generator at its own eight wavefronts per SIMD doubled in length and stretched the day by more than the reset
-// it hid (93.6 -> 101.6 us).  With 56 KB a workgroup, two fit a CU and leave the day's wavefronts their room:
-// 85.5 us on that box (54 - 60 KB alike; 41 KB, three a CU: 93.6; 64 KB, which leaves 32 KB: 98.2).  The lean
-// family's day is one wavefront per SIMD and was shorter beside the uncapped generator (N = 8: 114.9 us, capped
-// 117.2 - 118.3), so a forced overlap there is not capped.
-inline size_t overlapped_generator_lds(const StepPlan &pl) { return pl.family == STEP_WIDE ? 56u * 1024u : 0u; }
-// The same beside day_station_kernel (station_day: the graph's days run that kernel), which stages its table rows
-// behind its tiles: 5,880 B a wavefront, 6,400 B as a CU allocates LDS (blocks of 1,280 B), and eight of those fit a
-// CU's 160 KB beside two generator workgroups of up to 55 KB.  Measured beside that kernel, device time per day
-// (profiles/day_station_step_ab.txt): 56 KB 87.0 us (a CU holds seven of the day's wavefronts), 54 KB 76.1 - 77.3,
-// 52 KB 86.0 - 87.1 (three generator workgroups fit a CU where they arrive first).
-inline size_t overlapped_generator_lds(const StepPlan &pl, bool station_day) {
-    return station_day ? 54u * 1024u : overlapped_generator_lds(pl);
-}
-// Day d of `days` in such a graph: the day slot it is generated into and stepped in (0: the handle's own
-// buffers, 1: the shadow's -- the last day is always in slot 0, so after a replay the loaded day is where every
-// other call expects it); the day index its generator draws, as an offset from the day counter at launch (the
-// overlapped generators all read the counter before anything advances it); whether the day's first step advances
-// the counter (Params::bump_day); and the amount a bump node behind the day's generator adds.  Per replay the
-// counter advances by `days` in both forms.
-struct DayShape {
-    int slot, day_delta, bump_day, bump_node;
-};
-inline DayShape day_shape(bool overlapped, int days, int d) {
-    if (!overlapped) return {0, 0, 1, 0};
-    const bool last = d == days - 1;
-    return {(days - 1 - d) & 1, d, last ? 1 : 0, last ? days - 1 : 0};
-}
 
 // The name rocprofv3 reports for a plan's day kernel; an empty string where it has none.
 inline int day_plan_name(const StepPlan &pl, bool trajectory, char *buf, int len) {

@@ -228,6 +228,7 @@ EXPORTS = {
     "sng_graph_step_nodes": (ctypes.c_int, [ctypes.c_void_p]),
     "sng_graph_reset_overlapped": (ctypes.c_int, [ctypes.c_void_p]),
     "sng_graph_day_kernel_name": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]),
+    "sng_graph_describe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
     "sng_graph_destroy": (None, [ctypes.c_void_p]),
     "sng_time_step_kernels": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.POINTER(SngInfo), ctypes.c_int32, c_float_p,
@@ -358,6 +359,17 @@ def lib():
 
 class NativeError(RuntimeError):
     pass
+
+
+def graph_describe(g):
+    """sng_graph_describe's text for a graph handle: one line per captured node."""
+    n = lib().sng_graph_describe(g, None, 0)
+    if n < 0:
+        raise NativeError(f"libsng error {n}: sng_graph_describe")
+    buf = ctypes.create_string_buffer(n + 1)
+    if lib().sng_graph_describe(g, buf, len(buf)) != n:
+        raise NativeError("sng_graph_describe: the graph changed between two calls")
+    return buf.value.decode()
 
 
 def check(rc, handle=None):

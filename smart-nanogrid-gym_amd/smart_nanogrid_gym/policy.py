@@ -776,6 +776,10 @@ class ClosedLoopGraph(_Handle):
         step)."""
         return int(lib().sng_graph_step_nodes(self._g))
 
+    def describe(self):
+        """The captured graph as text (sng_graph_describe): a line per node with its kernel, geometry and edges."""
+        return _native.graph_describe(self._g)
+
     def launch(self, stream=None):
         if self.actor._p is None:   # the graph reads the actor's device image and its clipped-actions block
             raise RuntimeError("the actor was closed: a ClosedLoopGraph needs it for every launch")

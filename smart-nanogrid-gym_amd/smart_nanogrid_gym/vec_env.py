@@ -1001,6 +1001,10 @@ class EpisodeGraph:
         """Whether the graph generates day d + 1 while day d is stepped (include/sng.h, sng_graph_create)."""
         return bool(lib().sng_graph_reset_overlapped(self._g))
 
+    def describe(self):
+        """The captured graph as text (sng_graph_describe): a line per node with its kernel, geometry and edges."""
+        return _native.graph_describe(self._g)
+
     def launch(self, stream=None):
         s = _stream_handle(self.venv.device) if stream is None else ctypes.c_void_p(stream)
         if self.trajectory and not self.with_reset:   # the loaded day's t = 0 observation, ahead of the graph

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "sng_policy_net_host.h"
-#include "sng_step_plan.h"
+#include "sng_graph_form.h"
 
 using namespace sng;
 

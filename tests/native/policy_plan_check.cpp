@@ -1,11 +1,11 @@
-// CPU listing of the form a captured policy day takes (sng_step_plan.h, policy_day_form), for
+// CPU listing of the form a captured policy day takes (sng_graph_form.h, policy_day_form), for
 // tests/test_policy_cpu.py: one line per configuration, "N v2x noise legacy dt_pow2 packed req_stream req_zero diag
 // lanes trajectory step_nodes forced | step kernel name | fused or nodes | compiled or -", over the configurations
 // of day_plan_check.cpp, each without and with SNG_GRAPH_STEP_NODES and SNG_GRAPH_POLICY_FUSED.  "compiled": the
 // plan has day_lean_policy_kernel (whatever the flags).
 #include <cstdio>
 
-#include "sng_step_plan.h"
+#include "sng_graph_form.h"
 
 using namespace sng;
 

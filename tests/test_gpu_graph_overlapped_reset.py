@@ -1,4 +1,4 @@
-"""GPU: the overlapped reset graph (sng_graph_create; csrc/sng_step_plan.h reset_overlapped) -- day d + 1 generated
+"""GPU: the overlapped reset graph (sng_graph_create; csrc/sng_graph_form.h reset_overlapped) -- day d + 1 generated
 into a second day slot while day d is stepped -- against the serial chain of the same days
 (EpisodeGraph(serial_reset=True), SNG_GRAPH_SERIAL_RESET).
 
@@ -36,7 +36,7 @@ STATIONS = {
     # name: (env kwargs, EpisodeGraph kwargs, step nodes per day)
     "wide10": (KW10, {}, 1),
     "wide10_step_nodes": (KW10, dict(step_nodes=True), 24),
-    # the lean stations' default is the serial chain (csrc/sng_step_plan.h): overlapped by the flag
+    # the lean stations' default is the serial chain (csrc/sng_graph_form.h): overlapped by the flag
     "lean8": (KW8, dict(overlapped_reset=True), 1),
     "wide10_req": (dict(KW10, enable_requested_state_of_charge=True), {}, 1),
 }

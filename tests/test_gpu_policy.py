@@ -128,7 +128,7 @@ def test_create_refuses_what_the_contract_excludes():
 # -------------------------------------------------------------------------------------- 2. closed-loop day, exact
 DAY_CASES = {
     # name: (station, rng, E, step_nodes of the plan's default form, step_nodes with fused=True): 2 T = the node
-    # form, 1 = the fused day (csrc/sng_step_plan.h policy_day_form: the lean plans have it, none has it by default)
+    # form, 1 = the fused day (csrc/sng_graph_form.h policy_day_form: the lean plans have it, none has it by default)
     "n1": (station(1), "device", 70, 2 * T, 1),
     "n4": (station(4), "device", 70, 2 * T, 1),
     "n8": (station(8), "device", 70, 2 * T, 1),

@@ -1,5 +1,5 @@
-"""The shape of a captured reset graph (csrc/sng_step_plan.h: reset_overlapped, day_shape), listed on the CPU by
-tests/native/graph_shape_check.cpp for every configuration of the step-plan table.
+"""The form of a captured graph of days (csrc/sng_graph_form.h: graph_form, reset_overlapped, day_shape, day_blocks),
+listed on the CPU by tests/native/graph_shape_check.cpp for every configuration of the step-plan table.
 
 Which graphs generate day d + 1 beside day d's steps is one host-only decision: two days or more, no kept
 trajectory, no SNG_GRAPH_SERIAL_RESET, a device reset that is one launch (the t = 0 observation tile of the
@@ -7,11 +7,17 @@ generator's extra blocks within 32 KB), and a plan whose day measured shorter th
 SNG_GRAPH_OVERLAPPED_RESET.  The day slots rotate so that the last day of a replay is always in the
 handle's own buffers (slot 0), and the day counter advances by `days` per replay in both forms, with the same day
 indices drawn.
+
+graph_form composes these and the per-kernel predicates of sng_step_plan.h into the one answer a capture follows: which
+node steps a day, whether the resets overlap, the generators' LDS, the nodes a day and the day kernel's name.  The listing
+holds every GraphForm field beside the raw predicates, for every configuration x policy kind x reset x subset of the
+other six SNG_GRAPH_* bits x days 1 .. 3, and the rules are composed again here, on every line.
 """
 import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,29 +26,51 @@ DAYS = range(1, 6)
 OVERLAPPING = ("void sng::step_wide_kernel<10,",)
 
 
-@pytest.fixture(scope="module")
-def listing(tmp_path_factory):
+NS = (1, 2, 3, 4, 5, 8, 10, 16, 17, 50, 128)
+# sng_step_plan.h DayFamily, sng_graph_form.h PolicyDayForm, PolicyKind and DayNode
+DAY_NONE, DAY_WIDE, DAY_LEAN = 0, 1, 2
+POLICY_FUSED = 1
+POLICY_NONE, POLICY_MLP, POLICY_NET = 0, 1, 2
+STEP_NODES, KERNEL_LEAN, KERNEL_WIDE, KERNEL_STATION, POLICY_NODES, POLICY_FUSED_DAY = range(6)
+
+
+def build(tmp_path_factory, name, *flags):
     assert shutil.which("g++"), "g++ builds the host-only check"
-    exe = str(tmp_path_factory.mktemp("shape") / "graph_shape_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
+    exe = str(tmp_path_factory.mktemp("shape") / name)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I", CSRC, "-I", os.path.join(ROOT, "include"),
                     os.path.join(ROOT, "tests", "native", "graph_shape_check.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    return exe
+
+
+def run(exe, *args):
+    out = subprocess.run([exe, *args], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.returncode, out.stderr)
-    plans, shapes = [], {}
-    for line in out.stdout.splitlines():
+    return out.stdout
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return build(tmp_path_factory, "graph_shape_check", "-O2")
+
+
+@pytest.fixture(scope="module")
+def listing(exe):
+    plans, shapes, blocks = [], {}, {}
+    for line in run(exe).splitlines():
         parts = [x.strip() for x in line.split("|")]
         head = parts[0].split()
         if head[0] == "plan":
             fused, lds = (int(x) for x in parts[2].split())
             plans.append((tuple(int(x) for x in head[1:]), parts[1], fused, lds, parts[3].split()))
         else:
-            assert head[0] == "shape"
-            shapes[tuple(int(x) for x in head[1:])] = tuple(int(x) for x in parts[1].split())
-    return plans, shapes
+            assert head[0] in ("shape", "blocks")
+            into = shapes if head[0] == "shape" else blocks
+            into[tuple(int(x) for x in head[1:])] = tuple(int(x) for x in parts[1].split())
+    return plans, shapes, blocks
 
 
 def test_overlap_decision_for_every_plan(listing):
-    plans, _ = listing
+    plans = listing[0]
     assert len(plans) > 2000 and len({p[1] for p in plans}) > 50   # the whole table, many kernels
     fused_n, overlapping = set(), set()
     for key, kernel, fused, lds, flags in plans:
@@ -71,7 +99,7 @@ def test_overlap_decision_for_every_plan(listing):
 
 @pytest.mark.parametrize("days", DAYS)
 def test_slot_rotation_and_counter_amounts(listing, days):
-    _, shapes = listing
+    shapes = listing[1]
     serial = [shapes[(0, days, d)] for d in range(days)]
     assert serial == [(0, 0, 1, 0)] * days   # slot, day_delta, bump_day, bump_node
     over = [shapes[(1, days, d)] for d in range(days)]
@@ -84,3 +112,65 @@ def test_slot_rotation_and_counter_amounts(listing, days):
     assert [s[1] for s in over] == list(range(days))
     assert [s[2] for s in over] == [0] * (days - 1) + [1]
     assert [s[3] for s in over] == [0] * (days - 1) + [days - 1]
+
+
+def test_day_blocks_are_the_closed_forms(listing):
+    """Day d's offsets into [days][T + 1][E][O] observations, [days][T][E] rewards and [days][T][E][A] actions; without a
+    kept trajectory every step overwrites one block.  A noise source's buffer is [days][T][E][A] either way."""
+    blocks = listing[2]
+    O, A = 29, 11
+    assert len(blocks) == 2 * 3 * 2 * 2
+    for (traj, d, T, E), got in blocks.items():
+        kept = (d * (T + 1) * E * O, E * O, E, E * A, d * T * E, d * T * E * A)
+        assert got == (kept if traj else (0,) * 6) + (d * T * E * A,), (traj, d, T, E)
+
+
+@pytest.mark.parametrize("n", NS)
+def test_graph_form_composes_the_predicates(exe, n):
+    """Every line of `forms N`: the GraphForm fields are the raw predicates composed by graph_form's rules."""
+    seen_days, configs = set(), 0
+    for block in run(exe, "forms", str(n)).split("cfg ")[1:]:
+        head, body = block.split("\n", 1)
+        key, station, *plan_names = [x.strip() for x in head.split("|")]
+        assert station == "void sng::day_station_kernel<10, 2>" and len(plan_names) == 2, head
+        a = np.array(body.split(), dtype=np.int64).reshape(-1, 17)
+        assert len(a) == 3 * 2 * 64 * 3, key
+        configs += 1
+        policy, reset, sub, days = a[:, 0], a[:, 1] != 0, a[:, 2], a[:, 3]
+        with_reset, trajectory, overlapped, day, lds, nodes, name = (a[:, k] for k in range(4, 11))
+        kernel_of, station_sel, policy_form, reset_over, lds_plan, lds_station = (a[:, k] for k in range(11, 17))
+        step_nodes, traj = (sub & 1) != 0, (sub & 2) != 0
+        assert np.array_equal(np.unique(days), [1, 2, 3]) and np.array_equal(np.unique(sub), np.arange(64))
+        assert np.array_equal(with_reset != 0, reset) and np.array_equal(trajectory != 0, traj), key
+        # the name candidates: the plan has a day kernel's name exactly where it has a day kernel
+        for t in (0, 1):
+            kinds = np.unique(kernel_of[traj == bool(t)])
+            assert len(kinds) == 1, key
+            prefix = {DAY_NONE: "", DAY_WIDE: "void sng::day_wide_kernel<10, 2, ", DAY_LEAN: f"void sng::day_lean_kernel<{n}, "}
+            assert plan_names[t].startswith(prefix[int(kinds[0])]) and (plan_names[t] == "") == (kinds[0] == DAY_NONE), head
+        # no policy: a day kernel iff not STEP_NODES and the plan has one; the station's iff DAY_WIDE and selected
+        want = np.where(step_nodes | (kernel_of == DAY_NONE), STEP_NODES,
+                        np.where(kernel_of == DAY_LEAN, KERNEL_LEAN, np.where(station_sel != 0, KERNEL_STATION, KERNEL_WIDE)))
+        want = np.where(policy == POLICY_MLP, np.where(policy_form == POLICY_FUSED, POLICY_FUSED_DAY, POLICY_NODES), want)
+        want = np.where(policy == POLICY_NET, POLICY_NODES, want)
+        assert np.array_equal(day, want), key
+        want_over = (policy == POLICY_NONE) & reset & (reset_over != 0)
+        assert np.array_equal(overlapped != 0, want_over), key
+        assert np.array_equal(lds, np.where(want_over, np.where(day == KERNEL_STATION, lds_station, lds_plan), 0)), key
+        assert np.array_equal(nodes, np.where(day == STEP_NODES, 24, np.where(day == POLICY_NODES, 48, 1))), key
+        one_kernel = (policy == POLICY_NONE) & np.isin(day, (KERNEL_LEAN, KERNEL_WIDE, KERNEL_STATION))
+        assert np.array_equal(name, np.where(one_kernel, np.where(day == KERNEL_STATION, 1, 2), 0)), key
+        seen_days.update(np.unique(day[want_over]).tolist() if n == 8 else np.unique(day).tolist())
+    assert configs == 256 * (3 if n in (2, 4, 8, 10, 16, 50) else 1)
+    if n == 10:   # the default station's table holds every kind of day
+        assert seen_days == set(range(6))
+    if n == 8:    # a lean station's days overlap (when forced) as a kernel node and as step nodes
+        assert seen_days == {STEP_NODES, KERNEL_LEAN}
+
+
+def test_listing_runs_clean_under_sanitizers(tmp_path_factory, exe):
+    """The check is a stand-alone program: built with AddressSanitizer and UBSan it gives the same listings."""
+    san = build(tmp_path_factory, "graph_shape_check_san", "-O1", "-g", "-fsanitize=address,undefined",
+                "-fno-sanitize-recover=all")
+    assert run(san) == run(exe)
+    assert run(san, "forms", "10") == run(exe, "forms", "10")

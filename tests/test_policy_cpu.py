@@ -133,7 +133,7 @@ def test_policy_day_form_matches_the_design_table(tmp_path):
     assert set(table) == {"step_lean_kernel", "step_wide_kernel", "step_kernel"}, table
     assert table["step_lean_kernel"][1] == "fused" and table["step_wide_kernel"] == ("nodes", "nodes")
     exe = str(tmp_path / "policy_plan_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", *INCLUDES,
                     os.path.join(NATIVE, "policy_plan_check.cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, (out.returncode, out.stderr)

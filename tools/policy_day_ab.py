@@ -7,7 +7,7 @@ runs alternating (modelled on tools/day_kernel_ab.py):
   nodes    -- ClosedLoopGraph(step_nodes=True): T x (policy_kernel node, step node) per day;
   fused    -- ClosedLoopGraph(fused=True): day_lean_policy_kernel, one node a day, where the station has it (else the
               node form again; step_nodes says which);
-  default  -- ClosedLoopGraph(): what policy_day_form (csrc/sng_step_plan.h) gives the plan.
+  default  -- ClosedLoopGraph(): what policy_day_form (csrc/sng_graph_form.h) gives the plan.
 
   tools/policy_day_ab.py [--envs 65536] [--chargers 8] [--days 40] [--warmup 4] [--rounds 3] [--forms a,b]
   tools/policy_day_ab.py --profile [--chargers 8] [--out DIR]
