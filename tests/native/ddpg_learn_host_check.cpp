@@ -1,7 +1,10 @@
 // The host model of DDPG's gradient step (csrc/sng_ddpg_learn_host.h, learner_update_host) against naive loops written
 // from the formulas of include/sng.h, bitwise: nets (8, 8), (33, 65) and (400, 300), batches of 1, 63, 64, 65, S, S + 1
 // and 2 S + 37 rows (S = SNG_LEARNER_SEGMENT), critic input widths O + A of 13 and 160; the two narrower nets take two
-// updates in a row (the second with non-zero moments and t = 2).  The cases run on a few threads; build with -ffp-contract=off -pthread.
+// updates in a row (the second with non-zero moments and t = 2).  Four more cases take one state through batches in
+// descending order (2 S + 37, 200, 1, 64, 33, S + 1, 7), and through SNG_LEARNER_MAX_ROWS - 1 and SNG_LEARNER_MAX_ROWS
+// rows (64 segments, the last of S - 1 and of S rows) with 64 rows behind them.  The cases run on a few threads; build
+// with -ffp-contract=off -pthread.
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -231,9 +234,10 @@ bool same(const V &a, const V &b, const char *what, int h1, int h2, int B, int K
     return false;
 }
 
-void run_case(int h1, int h2, int B, int K) {
+// One state through one update per entry of `batches`, in that order.
+void run_case(int h1, int h2, const std::vector<int> &batches, int K) {
     const int A = K == 13 ? 2 : 51, O = K - A;
-    Rng r{(uint64_t)(h1 * 1000003 + h2 * 1009 + B * 31 + K)};
+    Rng r{(uint64_t)(h1 * 1000003 + h2 * 1009 + batches[0] * 31 + K)};
     State host, naive;
     host.actor.init(O, h1, h2, A, r, 2.f), host.actor_t.init(O, h1, h2, A, r, 2.f);
     host.critic.init(K, h1, h2, 1, r, 10.f), host.critic_t.init(K, h1, h2, 1, r, 10.f);
@@ -243,7 +247,8 @@ void run_case(int h1, int h2, int B, int K) {
     V lo(A, -1.f), hi(A, 1.f);
     const SngMlpNetSpec aspec{O, A, h1, h2, POLICY_RELU, SNG_MLP_OUT_SQUASH, lo.data(), hi.data()};
     const SngCriticSpec cspec{h1, h2, POLICY_RELU};
-    for (int update = 0; update < (h1 == 400 ? 1 : 2); ++update) {   // the widest net's chains once: they are the time
+    for (int update = 0; update < (int)batches.size(); ++update) {
+        const int B = batches[update];
         V obs((size_t)B * O), act((size_t)B * A), y(B), a_pi((size_t)B * A);
         for (float &v : obs) v = r.uniform(0.f, 1.f);
         for (float &v : act) v = r.uniform(-1.f, 1.f);
@@ -296,20 +301,29 @@ int main() {
                 }
     const int S = SNG_LEARNER_SEGMENT;
     struct Case {
-        int h1, h2, B, K;
+        int h1, h2;
+        std::vector<int> batches;
+        int K;
     };
     std::vector<Case> cases;
     const int nets[3][2] = {{400, 300}, {33, 65}, {8, 8}};
     for (auto &n : nets)
         for (int B : {2 * S + 37, S + 1, S, 65, 64, 63, 1})
-            for (int K : {160, 13}) cases.push_back({n[0], n[1], B, K});
+            for (int K : {160, 13})   // the widest net's chains once: they are the time
+                cases.push_back({n[0], n[1], n[0] == 400 ? std::vector<int>{B} : std::vector<int>{B, B}, K});
+    // one state through batches in descending and mixed order (the segments of an update are its own, whatever the
+    // update before it had), and the most segments there are: 64 whole ones, and 63 with one of S - 1 rows
+    cases.push_back({33, 65, {2 * S + 37, 200, 1, 64, 33, S + 1, 7}, 13});
+    cases.push_back({8, 8, {2 * S + 37, 200, 1}, 13});
+    cases.push_back({8, 8, {SNG_LEARNER_MAX_ROWS - 1}, 13});
+    cases.push_back({8, 8, {SNG_LEARNER_MAX_ROWS, 64}, 13});
     std::atomic<size_t> next{0};
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
     std::vector<std::thread> pool;
     for (unsigned i = 0; i < nt; ++i)
         pool.emplace_back([&] {
-            for (size_t c; (c = next++) < cases.size();) run_case(cases[c].h1, cases[c].h2, cases[c].B, cases[c].K);
+            for (size_t c; (c = next++) < cases.size();) run_case(cases[c].h1, cases[c].h2, cases[c].batches, cases[c].K);
         });
     for (auto &t : pool) t.join();
     if (g_failed) return 1;

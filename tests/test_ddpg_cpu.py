@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import ddpg_edge_cases as edge
 from policy_net_cases import net_f32_rounding_bound, net_f64, random_net_weights
 from smart_nanogrid_gym import _native, ddpg, policy
 
@@ -94,6 +95,89 @@ def test_sampling_refusals():
     assert L.sng_replay_host_indices(0, 0, 0, 10, 0, P) == -1 and b"batch" in err()
     assert L.sng_replay_host_indices(0, 0, 0, 10, 4, None) == -1
     assert L.sng_replay_host_indices(0, 0, 0, 10, 4, P) == 0
+
+
+# ----------------------------------------------------------------- the CPU halves of tests/test_gpu_ddpg_edges.py
+def test_the_push_cases_reach_all_three_copy_paths_for_every_instance():
+    """push_copy's path per copy, from the byte offsets alone (ddpg_edge_cases.copy_path): the populations and pushes
+    of the device test take the float32, the float64 -> float32 and the uint8 instance through the whole-vector, the
+    head-peeled and the element-only path each; the table in that file's docstring is this one."""
+    reached = edge.paths_reached()
+    assert set(reached) == {"f32", "f64_f32", "u8"}
+    for kind, paths in reached.items():
+        assert paths == set(edge.PATHS), (kind, paths)
+    # on 16-byte-aligned tensors the reward's copy is whole at every population: its other paths are DISPLACED's
+    by_array = {}
+    for case in edge.PUSH_CASES:
+        for _, number, array, run, path in edge.sequence_paths(*case):
+            assert run == 0   # no push of the sequence is cut by the wrap-around
+            by_array.setdefault((case[2], case[1], array), []).append(path)
+    for E in (1, 3, 67):
+        assert by_array[E, "1h", "obs"] == ["whole", "element", "element", "whole", "peeled"]
+        assert by_array[E, "1h", "done"] == ["whole", "whole", "element", "whole", "peeled"]
+    assert by_array[3, "2h", "obs"] == ["whole", "element", "element", "whole", "peeled"]
+    assert by_array[3, "2h", "done"] == ["whole", "element", "element", "whole", "peeled"]
+    for (E, interval, array), paths in by_array.items():
+        if E == 256 or array in ("actions", "reward"):
+            assert paths == ["whole"] * 5, (E, interval, array)
+    displaced = {(number, array): path for number, array, path in edge.displaced_paths()}
+    assert (displaced[0, "reward"], displaced[1, "reward"]) == ("peeled", "element")
+    assert (displaced[0, "actions"], displaced[1, "actions"]) == ("element", "peeled")
+    # the arithmetic itself, at hand-made offsets: 17 elements, float32 to float32
+    assert edge.copy_path(0, 0, 17, 4, 4) == "whole" and edge.copy_path(4, 4, 17, 4, 4) == "peeled"
+    assert edge.copy_path(0, 4, 17, 4, 4) == "element" and edge.copy_path(4, 4, 6, 4, 4) == "element"   # 3 + 3: no group
+    assert edge.copy_path(0, 8, 17, 8, 4) == "peeled" and edge.copy_path(8, 8, 17, 8, 4) == "element"
+    assert edge.copy_path(5, 5, 40, 1, 1) == "peeled" and edge.copy_path(0, 5, 40, 1, 1) == "element"
+
+
+def test_the_edge_samples_seed_exists_and_holds_what_it_promises():
+    T, E = 24, 70
+    samples = edge.partly_filled_samples(T, E)
+    seed = edge.seed_where(samples, T, E)
+    assert 0 <= seed < 10000
+    for counter, batch, n, slots in samples:
+        idx = ddpg.replay_host_indices(seed, 0, counter, n, batch)
+        assert idx.max() < n and ((idx // E) % T == T - 1).any()
+        assert set(np.unique(idx // (T * E))) == set(range(slots))
+    with pytest.raises(AssertionError, match="no seed"):
+        edge.seed_where([(0, 1, T * E, 2)], T, E, limit=50)   # one row cannot lie in two slots
+
+
+def test_the_sampling_law_at_the_device_tests_key():
+    """Env offset 2^33 + 5, seed 2^63 + 5, counter 2^32 + 9 on n = 5,040: in range, repeatable, a prefix law, and
+    another batch than at offset 0 (measured: 200 of 200 rows differ), at offset 5 (the low half alone) and at 2^33
+    (the high half alone)."""
+    n = 3 * 24 * 70
+    key = (edge.KEY_SEED, edge.KEY_OFFSET, edge.KEY_COUNTER)
+    idx = ddpg.replay_host_indices(*key, n, 200)
+    assert idx.min() >= 0 and idx.max() < n and np.unique(idx).size > 150
+    assert np.array_equal(idx, ddpg.replay_host_indices(*key, n, 200))
+    assert np.array_equal(idx[:64], ddpg.replay_host_indices(*key, n, 64))
+    for offset in (0, 5, 2 ** 33):
+        other = ddpg.replay_host_indices(edge.KEY_SEED, offset, edge.KEY_COUNTER, n, 200)
+        print(f"offset {offset}: {(other != idx).mean():.3f} of the rows differ")
+        assert (other != idx).mean() > 0.9, offset
+
+
+def test_special_rewards_cover_what_the_conversion_can_get_wrong():
+    reward, kinds = edge.special_rewards(1608)
+    with np.errstate(over="ignore"):
+        f32 = reward.astype(np.float32)
+    tiny = np.finfo(np.float32).tiny
+    assert np.isposinf(f32).any() and np.isneginf(f32).any() and not np.isinf(reward).any()
+    assert ((f32 != 0) & (np.abs(f32) < tiny)).sum() >= 4 * (1608 // reward[:40].size)   # subnormal results
+    assert (np.signbit(f32) & (f32 == 0)).any()
+    # the ties: exactly halfway in float64, and numpy rounds them to the neighbour with an even last bit
+    for name, lower_is_even in (("halfway, even below", True), ("halfway, odd below", False)):
+        for x in kinds[name]:
+            near = np.float32(x)
+            other = np.nextafter(near, np.float32(np.inf if x > near else -np.inf))
+            assert np.float64(near) != x and abs(x - np.float64(near)) == abs(np.float64(other) - x)
+            lower = near if abs(near) < abs(other) else other
+            assert (int(lower.view(np.uint32)) & 1 == 0) == lower_is_even
+            assert int(near.view(np.uint32)) & 1 == 0
+    for x in kinds["one float64 step off a float32"]:
+        assert np.float64(np.float32(x)) != x
 
 
 # ---------------------------------------------------------------------------------------------------------- host Q

@@ -53,7 +53,7 @@ def _run_native(tmp_path, name, extra):
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-pthread", *_fma_flag(), *extra,
                     *INCLUDES, SOURCE, "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "ddpg learn host ok 42 cases" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    assert out.returncode == 0 and "ddpg learn host ok 46 cases" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
     assert int(out.stdout.split()[-2]) > 1000000
 
 
@@ -321,6 +321,150 @@ def test_the_critic_loss_goes_down_on_a_fixed_batch():
     assert state["step"] == 50 and losses[-1] < losses[0], (losses[0], losses[-1])
     _, trace = torch_updates(sd, net, [(obs, act, y)] * 50, torch.float64)
     assert trace[-1][3] < trace[0][3], (trace[0][3], trace[-1][3])
+
+
+# ------------------------------------------------- the host-model halves of tests/test_gpu_ddpg_learn_edges.py
+AK, CK = ddpg.net_keys("actor.mu"), ddpg.net_keys("critic.qf0")
+ATK, CTK = ddpg.net_keys("actor_target.mu"), ddpg.net_keys("critic_target.qf0")
+EDGE_NET, EDGE_ROWS = (8, 8), 64
+
+
+def _copy(state):
+    return dict(step=state["step"], **{part: {k: a.copy() for k, a in state[part].items()}
+                                       for part in ("params", "exp_avg", "exp_avg_sq")})
+
+
+def _update(state, obs, act, y, a_pi, **hyper):
+    return ddpg.host_update(state, obs, act, y, a_pi, -1.0, 1.0, EDGE_NET, EDGE_NET, **dict(HYPER, **hyper))
+
+
+def _same(state, before, keys, part="params"):
+    return all(state[part][k].tobytes() == before[part][k].tobytes() for k in keys)
+
+
+def _moved(state, before, keys):
+    return all((state["params"][k] != before["params"][k]).any() for k in keys)
+
+
+def _host_a_pi(state, obs):
+    return policy.host_actions(obs, [state["params"][k] for k in AK], "relu", -1.0, 1.0, net_arch=EDGE_NET, squash=True)[0]
+
+
+@pytest.mark.parametrize("columns", ["all", "even"])
+def test_host_a_saturated_actor_passes_no_gradient_and_stays(columns):
+    """a_pi = +-1 given by hand: learn_dtanh's 1 - a a is 0, the actor's gradients vanish (all six, or the saturated
+    columns' rows of the last layer), Adam on g == 0 from zero moments returns the master's own bits (0 / (0 + eps)),
+    and the targets and the critic move all the same."""
+    state = ddpg.learner_host_state(initial_params(EDGE_NET), O, A, EDGE_NET, EDGE_NET)
+    obs, act, y = batch(3, EDGE_ROWS)
+    cols = np.arange(A)[::1 if columns == "all" else 2]
+    rest = np.setdiff1d(np.arange(A), cols)
+    a_pi = _host_a_pi(state, obs)
+    assert (np.abs(a_pi) < 1).all()
+    a_pi[:, cols] = np.where(np.arange(cols.size) % 2 == 0, 1.0, -1.0).astype(np.float32)
+    before = _copy(state)
+    out = _update(state, obs, act, y, a_pi)
+    g = out["grads"]
+    assert not g["actor.mu.4.weight"][cols].any() and not g["actor.mu.4.bias"][cols].any()
+    assert all(g[k].any() for k in CK) and _moved(state, before, CK + CTK + ATK)
+    if columns == "all":
+        assert not any(g[k].any() for k in AK)
+        assert _same(state, before, AK) and _same(state, before, AK, "exp_avg") and _same(state, before, AK, "exp_avg_sq")
+        assert not any(state["exp_avg"][k].any() or state["exp_avg_sq"][k].any() for k in AK)
+    else:
+        assert g["actor.mu.4.weight"][rest].any(axis=1).all() and (g["actor.mu.4.bias"][rest] != 0).all()
+        assert all(g[k].any() for k in AK) and _moved(state, before, AK)
+
+
+def test_host_a_dead_critic_layer_stops_both_backward_passes():
+    """critic b1 = -100: the pattern the device test asserts, on the host model."""
+    sd = initial_params(EDGE_NET)
+    sd["critic.qf0.0.bias"] = np.full(8, -100.0, np.float32)
+    state = ddpg.learner_host_state(sd, O, A, EDGE_NET, EDGE_NET)
+    obs, act, y = batch(3, EDGE_ROWS)
+    b2 = state["params"]["critic.qf0.2.bias"]
+    assert (b2 > 0).any()
+    before = _copy(state)
+    out = _update(state, obs, act, y, _host_a_pi(state, obs))
+    dead = ["critic.qf0.0.weight", "critic.qf0.0.bias", "critic.qf0.2.weight"] + AK
+    alive = ["critic.qf0.2.bias", "critic.qf0.4.weight", "critic.qf0.4.bias"]
+    assert not any(out["grads"][k].any() for k in dead) and _same(state, before, dead)
+    assert all(out["grads"][k].any() for k in alive) and _moved(state, before, alive)
+    assert (out["grads"]["critic.qf0.2.bias"] != 0).tolist() == (b2 > 0).tolist()
+    assert np.unique(out["q"]).size == 1 and np.unique(out["q_pi"]).size == 1
+
+
+def test_host_targets_equal_to_q_leave_the_critic_to_its_moments():
+    """y = Q(s, a): the update's q is host_q on the same weights bit for bit (which is what lets the device test take
+    y from critic.q), dq, the loss and the critic's gradients are exactly zero, the critic stays bit for bit on a
+    first step and moves by its moments alone after two ordinary ones."""
+    state = ddpg.learner_host_state(initial_params(EDGE_NET), O, A, EDGE_NET, EDGE_NET)
+    obs, act, y = batch(3, EDGE_ROWS)
+
+    def settled():
+        before = _copy(state)
+        q = ddpg.host_q(obs, act, [state["params"][k] for k in CK], EDGE_NET)
+        out = _update(state, obs, act, q, _host_a_pi(state, obs))
+        assert out["q"].tobytes() == q.tobytes()
+        assert not out["dq"].any() and out["critic_loss"] == 0.0 and not any(out["grads"][k].any() for k in CK)
+        assert all(out["grads"][k].any() for k in AK)
+        return before
+    before = settled()
+    assert _same(state, before, CK) and _moved(state, before, AK + CTK)
+    assert not any(state["exp_avg"][k].any() or state["exp_avg_sq"][k].any() for k in CK)
+    for i in range(2):
+        o2, a2, y2 = batch(4 + i, EDGE_ROWS)
+        _update(state, o2, a2, y2, _host_a_pi(state, o2))
+    before = settled()
+    assert _moved(state, before, CK) and state["step"] == 4
+
+
+def test_host_tau_at_both_ends():
+    obs, act, y = batch(3, EDGE_ROWS)
+    runs = {}
+    for tau in (0.005, 1.0, 0.0):
+        state = ddpg.learner_host_state(initial_params(EDGE_NET), O, A, EDGE_NET, EDGE_NET)
+        before = _copy(state)
+        runs[tau] = (state, before, _update(state, obs, act, y, _host_a_pi(state, obs), tau=tau))
+    ref, _, ref_out = runs[0.005]
+    for tau in (1.0, 0.0):
+        state, before, out = runs[tau]
+        assert _same(state, ref, AK + CK) and all(out["grads"][k].tobytes() == ref_out["grads"][k].tobytes() for k in AK + CK)
+        for k, kt in zip(AK + CK, ATK + CTK):
+            want = state["params"][k] if tau == 1.0 else before["params"][kt]
+            assert state["params"][kt].tobytes() == want.tobytes() != ref["params"][kt].tobytes(), (tau, kt)
+
+
+def test_host_resume_from_a_copied_state_and_late_steps():
+    """A state copied through learner_host_state(exp_avg=, exp_avg_sq=, step=) continues bit for bit; random moments
+    with step = 1, 999, 10^6 and 2^40 (beta^t underflows in the last two) stay finite and move every tensor."""
+    net = (33, 65)
+    state = ddpg.learner_host_state(initial_params(net), O, A, net, net)
+    batches = [batch(10 + i, EDGE_ROWS) for i in range(5)]
+    a_pi = np.tanh(np.random.default_rng(5).uniform(-2, 2, (EDGE_ROWS, A))).astype(np.float32)
+    step = lambda st, b: ddpg.host_update(st, *b, a_pi, -1.0, 1.0, net, net, **HYPER)   # noqa: E731
+    for b in batches[:3]:
+        step(state, b)
+    resumed = ddpg.learner_host_state(state["params"], O, A, net, net, exp_avg=state["exp_avg"],
+                                      exp_avg_sq=state["exp_avg_sq"], step=state["step"])
+    assert resumed["step"] == 3 and resumed["exp_avg"][CK[0]] is not state["exp_avg"][CK[0]]
+    for b in batches[3:]:
+        one, two = step(state, b), step(resumed, b)
+        assert one["q"].tobytes() == two["q"].tobytes() and one["critic_loss"] == two["critic_loss"]
+    assert state["step"] == resumed["step"] == 5
+    for part in ("params", "exp_avg", "exp_avg_sq"):
+        assert all(state[part][k].tobytes() == resumed[part][k].tobytes() for k in state[part])
+    rng = np.random.default_rng(6)
+    for t in (1, 999, 10 ** 6, 2 ** 40):
+        blank = ddpg.learner_host_state(initial_params(net, seed=t % 7), O, A, net, net)
+        m = {k: rng.normal(0.0, 0.1, a.shape).astype(np.float32) for k, a in blank["exp_avg"].items()}
+        vv = {k: rng.uniform(0.0, 1e-3, a.shape).astype(np.float32) for k, a in blank["exp_avg_sq"].items()}
+        st = ddpg.learner_host_state(blank["params"], O, A, net, net, exp_avg=m, exp_avg_sq=vv, step=t)
+        before = _copy(st)
+        out = step(st, batches[0])
+        assert st["step"] == t + 1 and np.isfinite(out["critic_loss"])
+        assert all(np.isfinite(a).all() for part in ("params", "exp_avg", "exp_avg_sq") for a in st[part].values())
+        assert _moved(st, before, AK + CK + ATK + CTK)
 
 
 # ------------------------------------------------------------------------------------------------------- refusals

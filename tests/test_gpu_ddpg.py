@@ -29,15 +29,16 @@ BASE = dict(charging_mode="bounded", vehicle_uncharged_penalty_mode="sparse", pv
             battery_system_available_in_model=True)
 
 
-def make_env(N, interval="1h"):
-    return SmartNanogridVecEnv(E, seed=SEED, rng="device", number_of_chargers=N, time_interval=interval, **BASE)
+def make_env(N, interval="1h", E=E, env_offset=0):
+    return SmartNanogridVecEnv(E, seed=SEED, rng="device", number_of_chargers=N, time_interval=interval,
+                               env_offset=env_offset, **BASE)
 
 
 def host(x):
     return x.cpu().numpy()
 
 
-def trajectory(v, seed):
+def trajectory(v, seed, E=E):
     """test_gpu_ppo_net_rollout's synthetic trajectory with stored actions in [-1, 1] beside it: (obs, actions,
     reward float64, done uint8) of DAYS days."""
     obs, reward, done, _, _ = synthetic(v, seed)
@@ -49,9 +50,9 @@ def trajectory(v, seed):
 class Mirror:
     """The ring in numpy: the contract's bookkeeping and layout."""
 
-    def __init__(self, v, capacity):
+    def __init__(self, v, capacity, E=E):
         T = v.timesteps
-        self.capacity, self.head, self.filled, self.T = capacity, 0, 0, T
+        self.capacity, self.head, self.filled, self.T, self.E = capacity, 0, 0, T, E
         self.obs = np.zeros((capacity, T + 1, E, v.obs_dim), np.float32)
         self.actions = np.zeros((capacity, T, E, v.act_dim), np.float32)
         self.reward = np.zeros((capacity, T, E), np.float32)
@@ -66,10 +67,10 @@ class Mirror:
         self.filled = min(self.filled + obs.shape[0], self.capacity)
 
     def __len__(self):
-        return self.filled * self.T * E
+        return self.filled * self.T * self.E
 
     def gather(self, idx):
-        T = self.T
+        T, E = self.T, self.E
         slot, t, e = idx // (T * E), (idx // E) % T, idx % E
         return (self.obs[slot, t, e], self.actions[slot, t, e], self.obs[slot, t + 1, e],
                 self.done[slot, t, e].astype(np.float32)[:, None], self.reward[slot, t, e][:, None])
@@ -79,11 +80,11 @@ class Mirror:
                    for n in ("obs", "actions", "reward", "done"))
 
 
-def filled_ring(v, seed=0):
+def filled_ring(v, seed=0, E=E):
     """A ring of three slots after two pushes of two days, and its mirror."""
-    ring, mirror = ReplayRing(v, CAPACITY, seed=seed), Mirror(v, CAPACITY)
+    ring, mirror = ReplayRing(v, CAPACITY, seed=seed), Mirror(v, CAPACITY, E)
     for s in (1, 2):
-        traj = trajectory(v, s)
+        traj = trajectory(v, s, E)
         ring.push(*[torch.from_numpy(a).to(v.device) for a in traj])
         mirror.push(*traj)
     return ring, mirror
